@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: Groth16 proofs/sec on a 2^20-constraint MiMC-chain R1CS over BN254 (BASELINE.json configs[1]).
 
-    python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,8 @@ A "step" is one pass of the hot path over one batch of synthetic input: one comp
 chain live in the transformed H / L queries, same proof bytes —, five MSMs incl. the G2 one, assembly -> 3 affine points)
 with the proving key, the circuit matrices and the witness z already resident in HBM.  Multi-GPU: one process
 per GPU, every rank proves independent proofs with the same resident key (weak scaling, no data-path
-collective); `value` = proofs of all ranks / max-over-ranks time.
+collective); `value` = proofs of all ranks / max-over-ranks time.  --dump-outputs DIR writes what the last timed step returned
+(the proof points, as exact 32-bit words in float64) to DIR/*.npy; the inputs are seeded, so two builds compare output for output.
 
 The JSON line also carries
   roofline      the dominant kernel (MSM bucket accumulation): algorithmic HBM bytes per launch / HIP-event time
@@ -29,9 +30,6 @@ import json
 import os
 import sys
 import time
-
-# must precede the first HIP call (torch.cuda): see ckb_zkp_amd/__init__.py
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 import numpy as np
 
@@ -109,6 +107,57 @@ def emit(out):
     print(compact_line(out), flush=True)
 
 
+DUMP_CAP = 64 << 20                  # --dump-outputs: bytes written in all
+
+
+def u32_words(a):
+    """uint64 limbs -> their little-endian 32-bit halves as float64 (every u32 is exact in a double)"""
+    return np.ascontiguousarray(a, dtype=np.uint64).view(np.uint32).astype(np.float64)
+
+
+def int_words(v, n):
+    """a Python integer (field element / coordinate, < 2^(32 n)) -> n little-endian 32-bit words as float64; None -> zeros"""
+    return np.array([0 if v is None else (v >> (32 * i)) & 0xFFFFFFFF for i in range(n)], dtype=np.float64)
+
+
+def proof_arrays(c, out, inf):
+    """(..., 8 fq_limbs) proof limbs + (..., 3) identity flags, as zkp_groth16_prove*(_dev) return them -> named arrays.
+    A, C: affine G1 (x, y); B: affine G2 (x.c0, x.c1, y.c0, y.c1); coordinates in Montgomery form, as the caller receives them."""
+    f = c.fq_limbs
+    out = np.asarray(out, dtype=np.uint64)
+    lead = out.shape[:-1]
+    return {"proof_a": u32_words(out[..., 0:2 * f]).reshape(*lead, 2, 2 * f),
+            "proof_b": u32_words(out[..., 2 * f:6 * f]).reshape(*lead, 4, 2 * f),
+            "proof_c": u32_words(out[..., 6 * f:8 * f]).reshape(*lead, 2, 2 * f),
+            "proof_infinity": np.asarray(inf, dtype=np.float64)}
+
+
+def marlin_arrays(c, proof):
+    """prove_native's dictionary -> named arrays: every field element / coordinate as 32-bit words (affine G1 points as
+    (x, y, is_identity) rows; a missing shifted commitment or rand_v is a zero row)"""
+    nq, nr = 2 * c.fq_limbs, 2 * c.fr_limbs
+
+    def pt(p):
+        return np.concatenate([int_words(None if p is None else p[0], nq), int_words(None if p is None else p[1], nq),
+                               [1.0 if p is None else 0.0]])
+    labels = list(proof["commitments"])
+    return {"marlin_commitments": np.stack([pt(proof["commitments"][l][0]) for l in labels]),
+            "marlin_shifted_commitments": np.stack([pt(proof["commitments"][l][1]) for l in labels]),
+            "marlin_evaluations": np.stack([int_words(v, nr) for v in proof["evaluations"]]),
+            "marlin_opening_w": np.stack([pt(w) for w, _ in proof["opening_proofs"]]),
+            "marlin_opening_rand_v": np.stack([int_words(v, nr) for _, v in proof["opening_proofs"]])}
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy (float64) per array"""
+    total = sum(np.asarray(a).nbytes for a in arrays.values())
+    assert total <= DUMP_CAP, f"{total} bytes of outputs > {DUMP_CAP}"
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+    log(f"outputs of the last timed step: {sorted(arrays)} -> {d}")
+
+
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
@@ -165,6 +214,8 @@ def bench_sharded(args, ctx, c, inst, params, z, rank, world, local):
         out = step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof_arrays(c, *out))
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.single_device_test else "cuda")
@@ -227,13 +278,14 @@ def bench_single_process_multi(args):
 
     def steps(k):
         if k <= 0:
-            return
+            return None
         if shard:
             for _ in range(k):
-                mpk.prove_raw(zds, rand_fr(1)[0], rand_fr(1)[0], z_on_device=True)
-        else:
-            # `k` steps = k proofs PER GPU, like one rank per GPU in the torchrun mode
-            mpk.prove_batch_raw([zds[i % n] for i in range(k * n)], rand_fr(k * n), rand_fr(k * n), z_on_device=True)
+                last = mpk.prove_raw(zds, rand_fr(1)[0], rand_fr(1)[0], z_on_device=True)
+            return last
+        # `k` steps = k proofs PER GPU, like one rank per GPU in the torchrun mode: the last step is the last proof of every GPU
+        outs, infs = mpk.prove_batch_raw([zds[i % n] for i in range(k * n)], rand_fr(k * n), rand_fr(k * n), z_on_device=True)
+        return outs[-n:], infs[-n:]
 
     def sync_all():
         for k in range(n):
@@ -259,9 +311,11 @@ def bench_single_process_multi(args):
     steps(args.warmup)
     sync_all()
     t0 = time.perf_counter()
-    steps(args.steps)
+    last = steps(args.steps)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof_arrays(c, *last))
     proofs = args.steps if shard else args.steps * n
     # per-device roofline of the dominant kernel: device 0 alone with its own copy of the whole key (outside the timed region)
     roofline = None
@@ -295,7 +349,7 @@ def bench_single_process_multi(args):
     m.close()
 
 
-def bench_marlin(ctx, curve="bn254", samples=87381, reps=3, verify=True, cpu=False):
+def bench_marlin(ctx, curve="bn254", samples=87381, reps=3, verify=True, cpu=False, dump=None):
     """BASELINE configs[3]: Marlin create_random_proof (|H| = 2^20, |K| = 2^21, |B| = 2^23, SRS degree 6.29 M) on one GPU:
     device-side indexer + device-resident prover, verifier messages derived from the Fiat-Shamir transcript round by
     round, the proof checked by the oracle's verifier (which re-derives them).  -> dict for the JSON line."""
@@ -330,6 +384,8 @@ def bench_marlin(ctx, curve="bn254", samples=87381, reps=3, verify=True, cpu=Fal
         runs.append({"total_s": time.perf_counter() - t, "rounds_s": sum(tm["ms_round"]) * 1e-3,
                      "commits_s": sum(tm["ms_commit"]) * 1e-3, "evaluations_s": tm["ms_evaluations"] * 1e-3,
                      "batch_open_s": tm["ms_open"] * 1e-3, "timing": tm})
+    if dump:
+        dump_outputs(dump, marlin_arrays(c, proof))
     best = min(runs[1:], key=lambda r_: r_["total_s"])
     tm = best.pop("timing")
     for r_ in runs:
@@ -729,7 +785,7 @@ def config_block(ctx, curve, log_n, steps, warmup, hbm_meas, skewed=False, cpu_r
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 64 Groth16 proofs; 3 Marlin proofs)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--log-n", type=int, default=20, help="QAP domain 2^k (k=20 is the BASELINE metric config)")
     ap.add_argument("--curve", default="bn254")
@@ -755,7 +811,12 @@ def main():
     ap.add_argument("--single-device-test", action="store_true",
                     help="TEST ONLY: every rank uses cuda:0 and the collectives run over gloo (exercises the N>1 code path "
                          "on a one-GPU box; the number it prints is not a multi-GPU measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (proof points as 32-bit words) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 3 if args.workload == "marlin" else 64
+    assert args.steps >= 1, "--steps must be at least 1"
     t_start = time.time()
 
     import torch
@@ -785,7 +846,7 @@ def main():
     c = get_curve(args.curve)
     ctx = Context(local)
     if args.workload == "marlin":
-        m = bench_marlin(ctx, args.curve, reps=max(args.steps if args.steps != 64 else 3, 1), cpu=not args.no_cpu_baseline)
+        m = bench_marlin(ctx, args.curve, reps=args.steps, cpu=not args.no_cpu_baseline, dump=args.dump_outputs)
         if rank == 0:
             emit({"metric": "Marlin proofs/sec (2^20 constraints, BN256)", "value": m["value"], "unit": "proofs/s",
                               "n_gpus": 1, "steps": m["runs"], "warmup": 1, "ms_per_step": round(m["s_per_proof"] * 1e3, 2),
@@ -830,12 +891,13 @@ def main():
         """k proofs through zkp_groth16_prove_batch_dev: the library pipelines consecutive proofs over its lanes
         (every proof is complete — all 3 points back on the host — when the call returns)."""
         if k <= 0:
-            return
+            return None
         if args.no_pipeline:
             for i in range(k):
-                pk.prove_raw(z_dev, rs[0][i], rs[1][i], z_on_device=True)
-            return
-        pk.prove_batch_raw([z_dev] * k, rs[0], rs[1])
+                last = pk.prove_raw(z_dev, rs[0][i], rs[1][i], z_on_device=True)
+            return last
+        outs, infs = pk.prove_batch_raw([z_dev] * k, rs[0], rs[1])
+        return outs[-1], infs[-1]
 
     # ---- N > 1: every rank proves the SAME (r, s) once before the timed region; the proofs must agree with rank 0's
     scale_parity = None
@@ -855,9 +917,11 @@ def main():
     steps(args.warmup, rs_warm)
     barrier()
     t0 = time.perf_counter()
-    steps(args.steps, rs_timed)
+    last = steps(args.steps, rs_timed)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof_arrays(c, *last))
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.single_device_test else "cuda")

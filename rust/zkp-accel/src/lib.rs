@@ -88,8 +88,7 @@ unsafe impl Send for Ctx {}
 unsafe impl Sync for Ctx {}
 
 impl Ctx {
-    /// Export `GPU_MAX_HW_QUEUES=16` in the process environment BEFORE the first HIP call: the library
-    /// does not touch the environment.
+    /// The library does not touch the process environment; `GPU_MAX_HW_QUEUES` is the host's choice.
     pub fn new(device_id: i32) -> Result<Self, Error> {
         let mut p: *mut ffi::zkp_ctx = ptr::null_mut();
         check(unsafe { ffi::zkp_ctx_create(&mut p, device_id as c_int) })?;

@@ -3,7 +3,6 @@ device-resident base-sharded Groth16 prover (every rank on cuda:0, collective ov
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np

@@ -109,3 +109,60 @@ def test_gpus_8_without_torchrun_reaches_the_in_library_multi_gpu_path(monkeypat
     with pytest.raises(_Stop):
         b.main()
     assert seen["ids"] == want_ids and seen["mode"] == want_mode
+
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
+def test_dumped_proof_words_give_back_the_limbs_exactly(tmp_path, curve):
+    """--dump-outputs: the proof limbs a caller receives, written as float64 32-bit words, decode to the same uint64 limbs"""
+    b = load_bench()
+    from ckb_zkp_amd.params import get_curve
+    c = get_curve(curve)
+    rng = np.random.default_rng(3)
+    out = rng.integers(0, 1 << 63, size=(2, 8 * c.fq_limbs), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    inf = np.array([[0, 1, 0], [1, 0, 0]], dtype=np.uint8)
+    b.dump_outputs(str(tmp_path / "d"), b.proof_arrays(c, out[-1], inf[-1]))
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert sorted(got) == ["proof_a", "proof_b", "proof_c", "proof_infinity"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    words = np.concatenate([got[k].reshape(-1) for k in ("proof_a", "proof_b", "proof_c")])
+    assert np.array_equal(words.astype(np.uint32).view(np.uint64), out[-1])
+    assert list(got["proof_infinity"]) == [1.0, 0.0, 0.0]
+    assert b.proof_arrays(c, out, inf)["proof_b"].shape == (2, 4, 2 * c.fq_limbs)
+
+
+def test_dumped_marlin_words_give_back_the_integers(tmp_path):
+    b = load_bench()
+    from ckb_zkp_amd.params import get_curve
+    c = get_curve("bn254")
+    x, y, e = c.q - 5, c.q - 7, c.r - 1
+    proof = {"commitments": {"w": ((x, y), None), "g_1": (None, (y, x))}, "evaluations": [e, 3],
+             "opening_proofs": [((x, y), e), ((y, x), None)]}
+    a = b.marlin_arrays(c, proof)
+    val = lambda row: sum(int(w) << (32 * i) for i, w in enumerate(row))
+    assert val(a["marlin_commitments"][0][:8]) == x and val(a["marlin_commitments"][0][8:16]) == y
+    assert a["marlin_commitments"][1][16] == 1.0 and a["marlin_shifted_commitments"][0][16] == 1.0
+    assert val(a["marlin_shifted_commitments"][1][:8]) == y
+    assert [val(r) for r in a["marlin_evaluations"]] == [e, 3]
+    assert [val(r) for r in a["marlin_opening_rand_v"]] == [e, 0]
+    with pytest.raises(AssertionError):
+        b.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(b.DUMP_CAP // 8 + 1)})
+
+
+@pytest.mark.parametrize("argv, want_steps", [(["--gpus", "8"], 64), (["--gpus", "8", "--steps", "5"], 5),
+                                              (["--gpus", "8", "--steps", "64", "--dump-outputs", "out"], 64),
+                                              (["--gpus", "8", "--workload", "marlin"], 3)])
+def test_steps_is_the_number_of_timed_steps(monkeypatch, argv, want_steps):
+    b = load_bench()
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    seen = {}
+
+    def spy(args):
+        seen.update(steps=args.steps, dump=args.dump_outputs)
+        raise _Stop()
+
+    monkeypatch.setattr(b, "bench_single_process_multi", spy)
+    with pytest.raises(_Stop):
+        b.main()
+    assert seen["steps"] == want_steps and seen["dump"] == ("out" if "--dump-outputs" in argv else None)

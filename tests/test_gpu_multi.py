@@ -235,7 +235,7 @@ def test_device_sharded_prover_multiprocess_gloo_on_one_gpu(world):
     """The product's sharded prover as REAL processes: `world` ranks launched by torch.distributed.run, every rank on
     cuda:0, DeviceShardedGroth16Prover.prove with its collective branch (all-gather of the device-resident partial sums,
     here staged over gloo) == the single-GPU proof computed by rank 0 with the whole key."""
-    env = dict(os.environ, PYTHONPATH=ROOT, GPU_MAX_HW_QUEUES="16")
+    env = dict(os.environ, PYTHONPATH=ROOT)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "tests", "dist_worker_gpu.py")]
@@ -251,7 +251,7 @@ def test_device_sharded_prover_multiprocess_gloo_on_one_gpu(world):
 
 
 def _bench_line(args, torchrun_world=0, timeout=1500):
-    env = dict(os.environ, PYTHONPATH=ROOT, GPU_MAX_HW_QUEUES="16")
+    env = dict(os.environ, PYTHONPATH=ROOT)
     if torchrun_world:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={torchrun_world}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + args

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """debug helper: one 2^k BN254 proof through zkp_groth16_prove_dev with serialised kernels"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ckb_zkp_amd import codec, groth16
 from ckb_zkp_amd.api import Context

@@ -10,7 +10,7 @@ ctx = Context(0)
 hold = ctx.to_device(np.zeros((1 << 20, 4), dtype=np.uint64))
 runs = int(sys.argv[1])
 for sw in sys.argv[2:]:
-    env = dict(os.environ, PYTHONPATH=os.getcwd(), GPU_MAX_HW_QUEUES="16")
+    env = dict(os.environ, PYTHONPATH=os.getcwd())
     for kv in sw.split(","):
         k, v = kv.split("=")
         env[k] = v
