@@ -153,6 +153,49 @@ class Context:
         _lib.check(fn(self.h, c.cid, _ptr(xy), _ptr(inf), _ptr(s), n, 1 if montgomery else 0, _ptr(out)), "zkp_msm_var")
         return out
 
+    def msm_var_batch_dev(self, curve, group: int, xy_ptrs, inf_ptrs, scalar_ptrs, ns, montgomery: bool = False) -> np.ndarray:
+        """zkp_msm_g*_var_batch_dev: len(ns) independent small variable-base MSMs over DEVICE pointers (inf_ptrs None, or a list
+        with None / 0 for entries without identity flags) -> (count, words) Jacobian limbs."""
+        c = get_curve(curve)
+        k = len(ns)
+        words = 3 * c.fq_limbs * (1 if group == 1 else 2)
+        out = np.zeros((k, words), dtype=np.uint64)
+        xa = (C.c_void_p * max(k, 1))(*[p or None for p in xy_ptrs])
+        sa = (C.c_void_p * max(k, 1))(*[p or None for p in scalar_ptrs])
+        ia = None if inf_ptrs is None else (C.c_void_p * max(k, 1))(*[p or None for p in inf_ptrs])
+        na = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        fn = self.lib.zkp_msm_g1_var_batch_dev if group == 1 else self.lib.zkp_msm_g2_var_batch_dev
+        _lib.check(fn(self.h, c.cid, k, xa, ia, sa, na, 1 if montgomery else 0, _ptr(out)), "zkp_msm_var_batch_dev")
+        return out
+
+    def msm_var_batch(self, curve, group: int, xys, infs, scalars, montgomery: bool = False) -> np.ndarray:
+        """Host convenience over msm_var_batch_dev: lists of numpy arrays (infs None, or a list with None entries) are uploaded,
+        run as one batch and freed.  Entry k uses min(len(xys[k]), len(scalars[k])) terms, as msm_var does."""
+        k = len(xys)
+        assert len(scalars) == k and (infs is None or len(infs) == k)
+        bufs, xp, ip, sp, ns = [], [], [], [], []
+        try:
+            for i in range(k):
+                xy, s = _c64(xys[i]), _c64(scalars[i])
+                n = min(xy.shape[0] if xy.ndim == 2 else 0, s.shape[0] if s.ndim == 2 else 0)
+                ns.append(n)
+                px = ps = pi = None
+                if n:
+                    px = self.to_device(xy[:n])
+                    bufs.append(px)
+                    ps = self.to_device(s[:n])
+                    bufs.append(ps)
+                    if infs is not None and infs[i] is not None:
+                        pi = self.to_device(np.ascontiguousarray(infs[i], dtype=np.uint8)[:n])
+                        bufs.append(pi)
+                xp.append(px)
+                sp.append(ps)
+                ip.append(pi)
+            return self.msm_var_batch_dev(curve, group, xp, None if infs is None else ip, sp, ns, montgomery)
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)
         xyz = _c64(xyz)

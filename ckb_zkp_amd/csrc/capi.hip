@@ -114,7 +114,7 @@ const char* zkp_status_string(int32_t s) {
 }
 
 // 0.2: ZKP_ERR_INVALID_POINT; partials slot 4 (L) = identity, slot 3 (H) = h + l (bucket chaining)
-const char* zkp_version(void) { return "zkp_accel 0.6 (gfx950)"; }
+const char* zkp_version(void) { return "zkp_accel 0.7 (gfx950)"; }
 
 int32_t zkp_ctx_get_config(zkp_ctx* ctx, zkp_ctx_config* out) {
   if (!ctx || !out) return ZKP_ERR_BAD_ARG;
@@ -435,6 +435,18 @@ int32_t zkp_msm_g2_var(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy, cons
                        size_t n, int32_t montgomery, uint64_t* out_xyz) {
   if (!out_xyz || (n && (!xy || !scalars))) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { msm_var_run(ctx, curve, 2, xy, inf, scalars, n, montgomery != 0, out_xyz); });
+}
+int32_t zkp_msm_g1_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* xy_dev,
+                                 const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns,
+                                 int32_t montgomery, uint64_t* out_xyz) {
+  if (count && (!xy_dev || !scalars_dev || !ns || !out_xyz)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { msm_var_batch_run(ctx, curve, 1, count, xy_dev, inf_dev, scalars_dev, ns, montgomery != 0, out_xyz); });
+}
+int32_t zkp_msm_g2_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* xy_dev,
+                                 const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns,
+                                 int32_t montgomery, uint64_t* out_xyz) {
+  if (count && (!xy_dev || !scalars_dev || !ns || !out_xyz)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { msm_var_batch_run(ctx, curve, 2, count, xy_dev, inf_dev, scalars_dev, ns, montgomery != 0, out_xyz); });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

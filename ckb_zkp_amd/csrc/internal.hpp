@@ -76,6 +76,10 @@ void msm_run_multi(zkp_ctx* ctx, size_t count, const uint64_t* handles, const si
                    size_t slot_words);
 void msm_var_run(zkp_ctx* ctx, int curve, int group, const uint64_t* xy_host, const uint8_t* inf_host,
                  const uint64_t* scalars_host, size_t n, bool montgomery, uint64_t* out_xyz_host);
+// count independent small MSMs over device-resident points / scalars, ns[k] <= ZKP_MSM_SMALL_MAX_G1 / _G2 (msm_small.hip)
+void msm_var_batch_run(zkp_ctx* ctx, int curve, int group, size_t count, const uint64_t* const* xy_dev,
+                       const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns, bool montgomery,
+                       uint64_t* out_xyz_host);
 void msm_free_all(zkp_ctx* ctx);
 void bases_drop(zkp_ctx* ctx, uint64_t handle);
 void point_fold(zkp_ctx* ctx, int curve, int group, const uint64_t* xyz_host, size_t k, uint64_t* out_xyz_host);

@@ -35,6 +35,8 @@
 
 #include "field_dev.hpp"
 #include "internal.hpp"
+#include "msm_digits.hpp"
+#include "msm_small.hpp"
 #include "msm_vtbl.hpp"
 
 namespace zkp {
@@ -298,46 +300,7 @@ bool bases_same_shape(zkp_ctx* ctx, uint64_t h1, uint64_t h2) {
   return a->curve == b->curve && a->n == b->n && a->c == b->c && a->W == b->W && a->wide == b->wide && a->cap == b->cap && a->lgk == b->lgk;
 }
 
-// ------------------------------------------------------------------------------------------- K5 digit scan
-// Signed c-bit digits of one scalar, produced on the fly inside BOTH level-1 sort passes (histogram and scatter):
-// the (bucket, point) entries are never materialised unsorted, so the scan reads 32 B per scalar (twice) and writes
-// one 8-B (low key, point | sign) word per entry.  ark's `into_repr()` (prover.rs:150-161) is the fused from_mont().
-struct DigitIter {
-  uint32_t v[8];
-  uint32_t carry;
-  // window w: the first `wide` windows are c bits wide, the others c - 1 (BasesEntry::wide); nb = 2^(c-1)
-  __device__ __forceinline__ void next(int w, int c, int wide, uint32_t nb, uint32_t& key, uint32_t& neg) {
-    const int cw = w < wide ? c : c - 1;
-    const int bit = w < wide ? w * c : wide * c + (w - wide) * (c - 1);
-    const int limb = bit >> 5, sh = bit & 31;
-    uint32_t d = 0;
-    if (limb < 8) {
-      uint64_t two = v[limb];
-      if (limb + 1 < 8) two |= (uint64_t)v[limb + 1] << 32;
-      d = (uint32_t)(two >> sh) & ((1u << cw) - 1);
-    }
-    d += carry;
-    neg = 0;
-    if (d > (1u << (cw - 1))) {
-      d = (1u << cw) - d;
-      neg = 1;
-      carry = 1;
-    } else {
-      carry = 0;
-    }
-    key = d == 0 ? nb : d - 1;                      // nb == sentinel (zero digit)
-  }
-};
-template <class FrP>
-__device__ __forceinline__ DigitIter load_scalar(const uint32_t* __restrict__ scalars, size_t i, int montgomery) {
-  Fp<FrP> s = Fp<FrP>::load(scalars + i * 8);
-  if (montgomery) s = s.from_mont();
-  DigitIter it;
-#pragma unroll
-  for (int l = 0; l < 8; l++) it.v[l] = s.v[l];
-  it.carry = 0;
-  return it;
-}
+// ------------------------------------------------------------------------------------------- K5 digit scan: msm_digits.hpp
 
 // ------------------------------------------------------------------------------------------- exclusive scan (u32)
 // three launches: per-2048-chunk sums -> one block scans the chunk sums (tiles of 1024 with a running carry) ->
@@ -1385,6 +1348,82 @@ void msm_var_run(zkp_ctx* ctx, int curve, int group, const uint64_t* xy_host, co
     ZKP_HIP(hipMemcpyAsync(sdev, scalars_host, n * 32, hipMemcpyHostToDevice, st));
   }
   msm_run_entry(ctx, &e, 0, sdev, n, montgomery, out_xyz_host, nullptr, nullptr, nullptr, 0, -1, nullptr);
+}
+
+const MsmSmallVtbl* msm_small_vtbl_c01();
+const MsmSmallVtbl* msm_small_vtbl_c02();
+const MsmSmallVtbl* msm_small_vtbl_c11();
+const MsmSmallVtbl* msm_small_vtbl_c12();
+const MsmSmallVtbl* msm_small_vtbl(int curve, int group) {
+  if (curve == ZKP_BN254 && group == 1) return msm_small_vtbl_c01();
+  if (curve == ZKP_BN254 && group == 2) return msm_small_vtbl_c02();
+  if (curve == ZKP_BLS12_381 && group == 1) return msm_small_vtbl_c11();
+  if (curve == ZKP_BLS12_381 && group == 2) return msm_small_vtbl_c12();
+  throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+}
+
+// `count` independent small variable-base MSMs over device-resident points and scalars in two launches (msm_small.hip).  Every
+// argument is checked before anything is queued, so an error leaves out_xyz_host untouched.
+void msm_var_batch_run(zkp_ctx* ctx, int curve, int group, size_t count, const uint64_t* const* xy_dev,
+                       const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns, bool montgomery,
+                       uint64_t* out_xyz_host) {
+  const MsmSmallVtbl* vt = msm_small_vtbl(curve, group);
+  const size_t cap = group == 1 ? ZKP_MSM_SMALL_MAX_G1 : ZKP_MSM_SMALL_MAX_G2;
+  for (size_t k = 0; k < count; k++) {
+    ZKP_REQUIRE(ns[k] <= cap, ZKP_ERR_BAD_ARG);
+    if (ns[k] == 0) continue;
+    ZKP_REQUIRE(xy_dev[k] && scalars_dev[k], ZKP_ERR_BAD_ARG);
+    ZKP_REQUIRE(((uintptr_t)xy_dev[k] | (uintptr_t)scalars_dev[k]) % 16 == 0, ZKP_ERR_BAD_ARG);   // 16-B vector loads
+  }
+  if (count == 0) return;
+  ZKP_REQUIRE(count <= ((size_t)1 << 24), ZKP_ERR_BAD_ARG);
+  // window bits: 8, or 9 from 2^13 points on (fewer windows once the 256 buckets are well filled); BLS12-381 G2 keeps 8 (LDS)
+  const bool c9_ok = !(curve == ZKP_BLS12_381 && group == 2);
+  std::vector<SmallDesc> d(count);
+  int c_max = 8;
+  for (size_t k = 0; k < count; k++) {
+    d[k].c = (c9_ok && ns[k] >= 8192) ? 9 : 8;
+    c_max = std::max(c_max, (int)d[k].c);
+  }
+  // slice: the largest power of two whose LDS fits, halved (down to 256 points) while the grid is small against 256 CUs
+  uint32_t slice = 4096;
+  while (small_lds_bytes(vt->bk_bytes, c_max, slice) > SMALL_LDS_MAX) slice >>= 1;
+  auto grid = [&](uint32_t sl) {
+    uint64_t total = 0;
+    for (size_t k = 0; k < count; k++)
+      if (ns[k]) total += (uint64_t)((256 + d[k].c) / d[k].c) * ((ns[k] + sl - 1) / sl);
+    return total;
+  };
+  while (slice > 256 && grid(slice) < 2048) slice >>= 1;
+  const uint64_t total_wg = grid(slice);
+  ZKP_REQUIRE(total_wg < ((uint64_t)1 << 31), ZKP_ERR_BAD_ARG);
+  uint32_t first = 0;
+  for (size_t k = 0; k < count; k++) {
+    SmallDesc& e = d[k];
+    e.n = (uint32_t)ns[k];
+    e.xy = reinterpret_cast<const uint32_t*>(ns[k] ? xy_dev[k] : nullptr);
+    e.inf = ns[k] && inf_dev ? inf_dev[k] : nullptr;
+    e.scalars = reinterpret_cast<const uint32_t*>(ns[k] ? scalars_dev[k] : nullptr);
+    e.W = ns[k] ? (256 + e.c) / e.c : 0;                 // W c > 256: the carry out of the top window is never lost
+    e.S = ns[k] ? (uint32_t)((ns[k] + slice - 1) / slice) : 0;
+    e.first_wg = first;
+    e.pad = 0;
+    first += e.W * e.S;
+  }
+  const size_t desc_bytes = (count * sizeof(SmallDesc) + 255) & ~(size_t)255;
+  const size_t part_bytes = ((size_t)total_wg * vt->bk_bytes + 255) & ~(size_t)255;
+  const size_t out_bytes = count * (size_t)vt->jac_words * 4;
+  char* buf = reinterpret_cast<char*>(ctx->msm_misc.get(desc_bytes + part_bytes + out_bytes));
+  SmallDesc* d_desc = reinterpret_cast<SmallDesc*>(buf);
+  char* d_part = buf + desc_bytes;
+  uint32_t* d_out = reinterpret_cast<uint32_t*>(d_part + part_bytes);
+  hipStream_t st = ctx->cur->stream;
+  ZKP_HIP(hipMemcpyAsync(d_desc, d.data(), count * sizeof(SmallDesc), hipMemcpyHostToDevice, st));
+  vt->run(st, d_desc, (uint32_t)count, (uint32_t)total_wg, slice, montgomery ? 1 : 0, small_lds_bytes(vt->bk_bytes, c_max, slice),
+          d_part, d_out);
+  ZKP_HIP(hipGetLastError());
+  ZKP_HIP(hipMemcpyAsync(out_xyz_host, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+  ZKP_HIP(hipStreamSynchronize(st));
 }
 
 void point_fold(zkp_ctx* ctx, int curve, int group, const uint64_t* xyz, size_t k, uint64_t* out) {

@@ -48,7 +48,8 @@ typedef enum { ZKP_NTT_FFT = 0, ZKP_NTT_IFFT = 1, ZKP_NTT_COSET_FFT = 2, ZKP_NTT
 typedef struct zkp_ctx zkp_ctx; /* opaque: device, stream, twiddle tables, scratch, resident bases */
 
 const char* zkp_status_string(int32_t status);
-/* "zkp_accel <major.minor> (gfx950)".  0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
+/* "zkp_accel <major.minor> (gfx950)".  0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
+ * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
  * watchdog (zkp_groth16_multi_info info[0] == 2); the multi-GPU entry points lock every member context.  0.5 (round 5): per-context lock (see Conventions); zkp_groth16_pk_upload_ex (ZKP_PK_KEEP_FORM); ZKP_MULTI_EXCHANGE=rccl also takes the RCCL
  * exchange with one rank; slots L / H of zkp_groth16_prove_partials_dev are only defined as a SUM for folded / evaluation-form /
@@ -187,6 +188,26 @@ int32_t zkp_msm_g1_var(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy_host,
                        const uint64_t* scalars_host, size_t n, int32_t montgomery, uint64_t* out_xyz);
 int32_t zkp_msm_g2_var(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy_host, const uint8_t* inf_host,
                        const uint64_t* scalars_host, size_t n, int32_t montgomery, uint64_t* out_xyz);
+/* `count` independent TRUE variable-base MSMs (curve/src/lib.rs:38-45 with fresh bases; hyrax IPA rounds, bulletproofs) in one
+ * call: result k = sum_{i < ns[k]} scalars_dev[k][i] * bases xy_dev[k][i].  Points, flags and scalars are in DEVICE memory (xy_dev[k]
+ * and scalars_dev[k] 16-byte aligned, as any element of a zkp_dev_alloc buffer is); nothing is precomputed or kept resident.
+ * inf_dev == NULL or inf_dev[k] == NULL: no identity flags for that entry.  montgomery != 0: Fr in Montgomery form (into_repr()
+ * fused), else canonical BigInteger256.  ns[k] == 0 -> identity.  Entries may alias (same bases or scalars for many k).
+ * Two kernel launches per call whatever `count` is: one wave per (entry, window, slice of <= 4096 points) with its 2^(c-1) XYZZ
+ * buckets in LDS (c = 8, or 9 from 2^13 points on), then one wave per entry for the window weights.  The caps bound the
+ * ~255-doubling tail and the slice partials per entry; above them the sort-based pipeline of zkp_msm_g*_var (c = 16, shared
+ * bucket reduction) does less work per point.  G2 points are twice as costly per addition, so its cap is half.
+ * ns[k] > cap -> ZKP_ERR_BAD_ARG (use zkp_msm_g*_var above that).  Every argument is checked before anything runs: on an error
+ * out_xyz is untouched.  Runs on the context's current stream and returns after the results are on the host.
+ * out_xyz: count Jacobian Montgomery results, 3 (G1) / 6 (G2) field elements each, host memory. */
+#define ZKP_MSM_SMALL_MAX_G1 65536
+#define ZKP_MSM_SMALL_MAX_G2 32768
+int32_t zkp_msm_g1_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* xy_dev,
+                                 const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns,
+                                 int32_t montgomery, uint64_t* out_xyz);
+int32_t zkp_msm_g2_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* xy_dev,
+                                 const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns,
+                                 int32_t montgomery, uint64_t* out_xyz);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
