@@ -196,6 +196,51 @@ class Context:
             for p in bufs:
                 self.dev_free(p)
 
+    def ipa_fold_dev(self, curve, l_xy_dev: int, l_inf_dev, r_xy_dev: int, r_inf_dev, n: int, a_mont, b_mont, out_xy_dev: int,
+                     out_inf_dev: int):
+        """zkp_g1_ipa_fold_dev: out[i] = (a L[i] + b R[i]).into_affine() over DEVICE pointers (G1; flags None / 0 = none; out may
+        equal L or R); a_mont, b_mont: one Fr element each, Montgomery (4 x u64)."""
+        a, b = _c64(a_mont), _c64(b_mont)
+        _lib.check(self.lib.zkp_g1_ipa_fold_dev(self.h, get_curve(curve).cid, C.c_void_p(l_xy_dev or 0), C.c_void_p(l_inf_dev or 0),
+                                                C.c_void_p(r_xy_dev or 0), C.c_void_p(r_inf_dev or 0), n, _ptr(a), _ptr(b),
+                                                C.c_void_p(out_xy_dev or 0), C.c_void_p(out_inf_dev or 0)), "zkp_g1_ipa_fold_dev")
+
+    def ipa_fold(self, curve, l_xy: np.ndarray, l_inf, r_xy: np.ndarray, r_inf, a_mont, b_mont):
+        """Host convenience over ipa_fold_dev: ((n, w) affine Montgomery, (n,) identity flags) of a L[i] + b R[i]."""
+        l_xy, r_xy = _c64(l_xy), _c64(r_xy)
+        n = l_xy.shape[0]
+        assert r_xy.shape == l_xy.shape
+        out = np.zeros_like(l_xy)
+        inf = np.zeros(n, dtype=np.uint8)
+        if n == 0:
+            return out, inf
+        bufs = []
+        try:
+            def up(a):
+                d = self.to_device(a)
+                bufs.append(d)
+                return d
+            li = None if l_inf is None else up(np.ascontiguousarray(l_inf, dtype=np.uint8)[:n])
+            ri = None if r_inf is None else up(np.ascontiguousarray(r_inf, dtype=np.uint8)[:n])
+            dl, dr, do, di = up(l_xy), up(r_xy), up(out), up(inf)
+            self.ipa_fold_dev(curve, dl, li, dr, ri, n, a_mont, b_mont, do, di)
+            self.d2h(out, do)
+            self.d2h(inf, di)
+            return out, inf
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+
+    def fr_dot_batch_dev(self, curve, a_ptrs, b_ptrs, ns) -> np.ndarray:
+        """zkp_fr_dot_batch_dev: <a_k, b_k> over DEVICE Fr vectors (Montgomery) -> (count, 4) uint64 Montgomery."""
+        k = len(ns)
+        out = np.zeros((k, 4), dtype=np.uint64)
+        aa = (C.c_void_p * max(k, 1))(*[p or None for p in a_ptrs])
+        ba = (C.c_void_p * max(k, 1))(*[p or None for p in b_ptrs])
+        na = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
+        _lib.check(self.lib.zkp_fr_dot_batch_dev(self.h, get_curve(curve).cid, k, aa, ba, na, _ptr(out)), "zkp_fr_dot_batch_dev")
+        return out
+
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)
         xyz = _c64(xyz)

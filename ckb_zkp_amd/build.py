@@ -51,6 +51,8 @@ for _c, _g in CONFIGS:
         _acc = ["-DZKP_ACC_UNSAT_G2"]                 # BLS12-381 G2 likewise (336 VGPRs, no spills: 14.4 vs 18.6 ms per 2^22 B-query accumulate)
     UNITS.append(("msm_acc.hip", f"msm_acc_c{_c}{_g}.o", _d + ["-DZKP_INLINE_MUL"] + _acc + UNROLL))
     UNITS.append(("msm_small.hip", f"msm_small_c{_c}{_g}.o", _d + UNROLL))   # batched small variable-base MSM (own launch table)
+for _c in (0, 1):
+    UNITS.append(("ipa.hip", f"ipa_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"] + UNROLL))       # IPA generator fold, G1 (own launch table)
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result",
          "-ffp-contract=off"]
 

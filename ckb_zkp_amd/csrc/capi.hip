@@ -7,6 +7,7 @@
 #include "ctx.hpp"
 #include "host_field.hpp"
 #include "internal.hpp"
+#include "ipa.hpp"
 
 using namespace zkp;
 
@@ -114,7 +115,7 @@ const char* zkp_status_string(int32_t s) {
 }
 
 // 0.2: ZKP_ERR_INVALID_POINT; partials slot 4 (L) = identity, slot 3 (H) = h + l (bucket chaining)
-const char* zkp_version(void) { return "zkp_accel 0.7 (gfx950)"; }
+const char* zkp_version(void) { return "zkp_accel 0.7.1 (gfx950)"; }
 
 int32_t zkp_ctx_get_config(zkp_ctx* ctx, zkp_ctx_config* out) {
   if (!ctx || !out) return ZKP_ERR_BAD_ARG;
@@ -447,6 +448,17 @@ int32_t zkp_msm_g2_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, 
                                  int32_t montgomery, uint64_t* out_xyz) {
   if (count && (!xy_dev || !scalars_dev || !ns || !out_xyz)) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { msm_var_batch_run(ctx, curve, 2, count, xy_dev, inf_dev, scalars_dev, ns, montgomery != 0, out_xyz); });
+}
+int32_t zkp_g1_ipa_fold_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_xy, const uint8_t* l_inf, const uint64_t* r_xy,
+                            const uint8_t* r_inf, size_t n, const uint64_t* a_host, const uint64_t* b_host, uint64_t* out_xy,
+                            uint8_t* out_inf) {
+  if (n && (!l_xy || !r_xy || !a_host || !b_host || !out_xy || !out_inf)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { ipa_vtbl(curve)->fold(ctx, l_xy, l_inf, r_xy, r_inf, n, a_host, b_host, out_xy, out_inf); });
+}
+int32_t zkp_fr_dot_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* a_dev,
+                             const uint64_t* const* b_dev, const size_t* ns, uint64_t* out_host) {
+  if (count && (!a_dev || !b_dev || !ns || !out_host)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_dot_batch(ctx, curve, count, a_dev, b_dev, ns, out_host); });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

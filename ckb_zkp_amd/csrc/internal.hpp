@@ -18,6 +18,9 @@ void ntt_free_tables(zkp_ctx* ctx);
 void fr_vec_op(zkp_ctx* ctx, int curve, int op, const uint64_t* a, const uint64_t* b, const uint64_t* k_host,
                uint64_t* out, size_t n);
 void fr_batch_inverse(zkp_ctx* ctx, int curve, uint64_t* v, size_t n);
+// count inner products <a[k], b[k]> of ns[k] Fr terms (device) -> out_host (Montgomery), two launches (poly.hip)
+void fr_dot_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* a, const uint64_t* const* b, const size_t* ns,
+                  uint64_t* out_host);
 void fr_spmv(zkp_ctx* ctx, int curve, const uint32_t* row_ptr, const uint32_t* col, const uint64_t* coeff, size_t nrows,
              const uint64_t* x, uint64_t* out);
 void fr_gather(zkp_ctx* ctx, const uint64_t* in, const int32_t* idx, size_t n, uint64_t* out);

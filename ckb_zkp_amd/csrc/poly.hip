@@ -259,6 +259,102 @@ void fr_vec_op(zkp_ctx* ctx, int curve, int op, const uint64_t* a, const uint64_
   ZKP_HIP(hipGetLastError());
 }
 
+// Batched inner products <a_k, b_k> (the `inner_product` calls of bullet_inner_product_proof, spartan/src/inner_product.rs:40-41):
+// launch 1 runs one workgroup per (entry, chunk of DOT_CHUNK terms) and leaves one partial sum per workgroup, launch 2 one workgroup
+// per entry that adds its partials.  Field addition is exact, so the order of the tree does not matter.
+constexpr int DOT_THREADS = 256, DOT_PER = 8, DOT_CHUNK = DOT_THREADS * DOT_PER;
+struct DotDesc {
+  const uint32_t* a;
+  const uint32_t* b;
+  uint32_t n;
+  uint32_t first_wg;           // entries without terms share first_wg with the next entry
+};
+template <class P>
+__device__ __forceinline__ Fp<P> dot_block_sum(Fp<P> acc, char* smem) {
+  using F = Fp<P>;
+  const int t = threadIdx.x;
+  acc.store(smem + t * 32);
+  __syncthreads();
+  for (int s = DOT_THREADS / 2; s > 0; s >>= 1) {
+    if (t < s) (F::load(smem + t * 32) + F::load(smem + (t + s) * 32)).store(smem + t * 32);
+    __syncthreads();
+  }
+  return F::load(smem);
+}
+template <class P>
+__global__ __launch_bounds__(DOT_THREADS) void dot_chunk_kernel(const DotDesc* __restrict__ descs, uint32_t count,
+                                                                uint32_t* __restrict__ partial) {
+  using F = Fp<P>;
+  __shared__ __attribute__((aligned(16))) char smem[DOT_THREADS * 32];
+  const uint32_t wg = blockIdx.x;
+  uint32_t lo = 0, hi = count - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (descs[mid].first_wg <= wg) lo = mid;
+    else hi = mid - 1;
+  }
+  const DotDesc d = descs[lo];
+  const size_t base = (size_t)(wg - d.first_wg) * DOT_CHUNK;
+  F acc = F::zero();
+#pragma unroll
+  for (int k = 0; k < DOT_PER; k++) {
+    const size_t i = base + (size_t)k * DOT_THREADS + threadIdx.x;
+    if (i < d.n) acc = acc + F::load(d.a + i * 8) * F::load(d.b + i * 8);
+  }
+  acc = dot_block_sum<P>(acc, smem);
+  if (threadIdx.x == 0) acc.store(partial + (size_t)wg * 8);
+}
+template <class P>
+__global__ __launch_bounds__(DOT_THREADS) void dot_final_kernel(const DotDesc* __restrict__ descs, const uint32_t* __restrict__ partial,
+                                                                uint32_t* __restrict__ out) {
+  using F = Fp<P>;
+  __shared__ __attribute__((aligned(16))) char smem[DOT_THREADS * 32];
+  const DotDesc d = descs[blockIdx.x];
+  const uint32_t chunks = (uint32_t)(((size_t)d.n + DOT_CHUNK - 1) / DOT_CHUNK);
+  F acc = F::zero();
+  for (uint32_t c = threadIdx.x; c < chunks; c += DOT_THREADS) acc = acc + F::load(partial + (size_t)(d.first_wg + c) * 8);
+  acc = dot_block_sum<P>(acc, smem);
+  if (threadIdx.x == 0) acc.store(out + (size_t)blockIdx.x * 8);
+}
+
+void fr_dot_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* a, const uint64_t* const* b, const size_t* ns,
+                  uint64_t* out_host) {
+  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  ZKP_REQUIRE(count <= ((size_t)1 << 24), ZKP_ERR_BAD_ARG);
+  std::vector<DotDesc> d(count);
+  uint64_t total = 0;
+  for (size_t k = 0; k < count; k++) {
+    ZKP_REQUIRE(ns[k] <= ((size_t)1 << 31), ZKP_ERR_BAD_ARG);
+    if (ns[k]) {
+      ZKP_REQUIRE(a[k] && b[k], ZKP_ERR_BAD_ARG);
+      ZKP_REQUIRE((((uintptr_t)a[k] | (uintptr_t)b[k]) & 15) == 0, ZKP_ERR_BAD_ARG);     // 16-B vector loads
+    }
+    d[k] = {reinterpret_cast<const uint32_t*>(ns[k] ? a[k] : nullptr), reinterpret_cast<const uint32_t*>(ns[k] ? b[k] : nullptr),
+            (uint32_t)ns[k], (uint32_t)total};
+    total += (ns[k] + DOT_CHUNK - 1) / DOT_CHUNK;
+    ZKP_REQUIRE(total < ((uint64_t)1 << 31), ZKP_ERR_BAD_ARG);
+  }
+  if (count == 0) return;
+  const size_t desc_bytes = (count * sizeof(DotDesc) + 255) & ~(size_t)255;
+  const size_t part_bytes = ((size_t)total * 32 + 255) & ~(size_t)255;
+  char* buf = reinterpret_cast<char*>(ctx->poly_tmp.get(desc_bytes + part_bytes + count * 32));
+  DotDesc* d_desc = reinterpret_cast<DotDesc*>(buf);
+  uint32_t* d_part = reinterpret_cast<uint32_t*>(buf + desc_bytes);
+  uint32_t* d_out = reinterpret_cast<uint32_t*>(buf + desc_bytes + part_bytes);
+  hipStream_t st = ctx->cur->stream;
+  ZKP_HIP(hipMemcpyAsync(d_desc, d.data(), count * sizeof(DotDesc), hipMemcpyHostToDevice, st));
+  auto launch = [&](auto tag) {
+    using P = decltype(tag);
+    if (total) hipLaunchKernelGGL(dot_chunk_kernel<P>, dim3((uint32_t)total), dim3(DOT_THREADS), 0, st, d_desc, (uint32_t)count, d_part);
+    hipLaunchKernelGGL(dot_final_kernel<P>, dim3((uint32_t)count), dim3(DOT_THREADS), 0, st, d_desc, d_part, d_out);
+  };
+  if (curve == ZKP_BN254) launch(Bn254Fr{});
+  else launch(Bls381Fr{});
+  ZKP_HIP(hipGetLastError());
+  ZKP_HIP(hipMemcpyAsync(out_host, d_out, count * 32, hipMemcpyDeviceToHost, st));
+  ZKP_HIP(hipStreamSynchronize(st));
+}
+
 // Marlin, second round (ahp/prover.rs:246-305) on the product domain D:   out = r_alpha * (eta_c z_a z_b + eta_a z_a + eta_b z_b) - t * z
 // from the evaluations over D of r_alpha, z_a, z_b, t, z (round 4: m(X) = eta_c z_a z_b + ... is formed pointwise instead of as
 // coefficients, which needed a product of its own: three transforms of size |D| / 2 and eight element-wise launches less).

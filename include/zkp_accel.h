@@ -48,7 +48,8 @@ typedef enum { ZKP_NTT_FFT = 0, ZKP_NTT_IFFT = 1, ZKP_NTT_COSET_FFT = 2, ZKP_NTT
 typedef struct zkp_ctx zkp_ctx; /* opaque: device, stream, twiddle tables, scratch, resident bases */
 
 const char* zkp_status_string(int32_t status);
-/* "zkp_accel <major.minor> (gfx950)".  0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
+/* "zkp_accel <major.minor> (gfx950)".  0.7.1: zkp_g1_ipa_fold_dev (IPA generator fold) / zkp_fr_dot_batch_dev (batched Fr inner
+ * products).  0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
  * watchdog (zkp_groth16_multi_info info[0] == 2); the multi-GPU entry points lock every member context.  0.5 (round 5): per-context lock (see Conventions); zkp_groth16_pk_upload_ex (ZKP_PK_KEEP_FORM); ZKP_MULTI_EXCHANGE=rccl also takes the RCCL
@@ -208,6 +209,24 @@ int32_t zkp_msm_g1_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, 
 int32_t zkp_msm_g2_var_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* xy_dev,
                                  const uint8_t* const* inf_dev, const uint64_t* const* scalars_dev, const size_t* ns,
                                  int32_t montgomery, uint64_t* out_xyz);
+/* IPA generator fold (spartan/src/inner_product.rs:71-74, hyrax/src/commitment.rs:550-552):
+ * out[i] = (a * L[i] + b * R[i]).into_affine() for i < n, BN254 / BLS12-381 G1.
+ * l_xy, r_xy, out_xy: n affine Montgomery points in DEVICE memory, the layout of zkp_bases_upload_g1 / zkp_msm_g1_var_batch_dev
+ * (16-byte aligned).  l_inf / r_inf: identity flags or NULL (= none).  out_inf: required.
+ * a_host, b_host: one Fr element each, Montgomery, host memory.  The same a and b apply to every i.
+ * Identities are written exactly as zkp_fixed_base_mul_g1 writes them (words and flag).
+ * out_xy may equal l_xy or r_xy, and out_inf may equal l_inf or r_inf (in-place fold).  Any other overlap -> ZKP_ERR_BAD_ARG.
+ * n == 0 -> ZKP_OK, nothing runs.  Every argument is checked before anything runs: on an error the outputs are untouched.
+ * One launch: one lane per point, GLV + joint-sparse-form digits of a and b planned once on the host, one batch inversion per
+ * 64 points.  Runs on the context's current stream and returns when out is written. */
+int32_t zkp_g1_ipa_fold_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_xy, const uint8_t* l_inf,
+                            const uint64_t* r_xy, const uint8_t* r_inf, size_t n,
+                            const uint64_t* a_host, const uint64_t* b_host, uint64_t* out_xy, uint8_t* out_inf);
+/* count inner products <a_k, b_k> of Fr Montgomery vectors in DEVICE memory (16-byte aligned), ns[k] terms each (0 -> zero);
+ * entries may alias.  out_host: count Fr elements, Montgomery.  Two launches whatever count is (spartan/src/inner_product.rs:40-41).
+ * Every argument is checked before anything runs.  Returns after the results are on the host. */
+int32_t zkp_fr_dot_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* a_dev,
+                             const uint64_t* const* b_dev, const size_t* ns, uint64_t* out_host);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
