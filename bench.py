@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Benchmark: Groth16 proofs/sec on a 2^20-constraint MiMC-chain R1CS over BN254 (BASELINE.json configs[1]).
 
-    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: one complete Groth16 proof
 (sparse A/B·z, 4 NTTs + pointwise on the evaluation-form key — the reference's witness_map is 7 NTTs; the last transform and the C
@@ -13,7 +13,11 @@ per GPU, every rank proves independent proofs with the same resident key (weak s
 collective); `value` = proofs of all ranks / max-over-ranks time.  --dump-outputs DIR writes what the last timed step returned
 (the proof points, as exact 32-bit words in float64) to DIR/*.npy; the inputs are seeded, so two builds compare output for output.
 
-The JSON line also carries
+A plain run does only what its headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, and the JSON line
+(metric, value, unit, ms_per_step, dtype, config).  Everything below, and every parity check (scale_parity, parity_check, the
+Marlin verifier), runs with --full only; the full record then also goes to DETAIL_PATH.
+
+With --full the JSON line also carries
   roofline      the dominant kernel (MSM bucket accumulation): algorithmic HBM bytes per launch / HIP-event time
   cpu_baseline  the C++ restatement of the reference algorithm (oracle/cpu, "port") on the host cores: the full 2^20 instance
                 when the host proves it in seconds (the GPU box: 256 threads, 2.8 s), else a 2^16 sample scaled linearly
@@ -94,8 +98,13 @@ def compact_line(out):
     return txt
 
 
-def emit(out):
-    """full record -> gpurun_out/bench_detail.json (merged back by gpurun; copied into profiles/ per round), compact line -> stdout"""
+def emit(out, detail=True):
+    """full record -> DETAIL_PATH (copied into profiles/ per round), compact line -> stdout.  detail=False (a plain run, whose
+    record is the line itself): no file is written."""
+    if not detail:
+        out["detail"] = None
+        print(compact_line(out), flush=True)
+        return
     try:
         os.makedirs(os.path.dirname(DETAIL_PATH), exist_ok=True)
         with open(DETAIL_PATH, "w") as f:
@@ -182,10 +191,11 @@ def bench_sharded(args, ctx, c, inst, params, z, rank, world, local):
         ctx.sync()
 
     z_dev = ctx.to_device(z)                                    # witness resident in HBM before the timed region
-    # scale_parity, checked BEFORE timing: the sharded proof of a fixed (r, s) == the proof rank 0 computes alone with the whole key
-    sharded = prover.prove(z_dev, r_, s_)                       # collective: every rank takes part
     scale_parity = roofline = None
-    if rank == 0:
+    if args.full:
+        # scale_parity, checked BEFORE timing: the sharded proof of a fixed (r, s) == the proof rank 0 computes alone with the whole key
+        sharded = prover.prove(z_dev, r_, s_)                   # collective: every rank takes part
+    if args.full and rank == 0:
         from ckb_zkp_amd import groth16
         pk0 = groth16.ProvingKey(ctx, params, inst)
         single = pk0.prove_raw(z_dev, codec_mont(c, r_), codec_mont(c, s_), z_on_device=True)
@@ -237,7 +247,7 @@ def bench_sharded(args, ctx, c, inst, params, z, rank, world, local):
             "exchange": {"kind": "gloo (host-staged, TEST ONLY)" if args.single_device_test else "rccl" if world > 1 else "none",
                          "ranks": world, "call": "torch.distributed.all_gather_into_tensor on device buffers" if world > 1 else None,
                          "bytes_per_rank": prover.pb},
-            "roofline": roofline, "cpu_baseline": recorded_cpu_baseline(c.name, args.log_n)})
+            "roofline": roofline, "cpu_baseline": recorded_cpu_baseline(c.name, args.log_n) if args.full else None}, detail=args.full)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -291,10 +301,12 @@ def bench_single_process_multi(args):
         for k in range(n):
             m.member(k).sync()
 
-    # scale_parity, checked BEFORE timing, with a fixed (r, s): shard — the proof over all devices == the proof device 0 computes alone
-    # with the whole key; throughput — the same proof from every device's replica
+    # scale_parity (--full), checked BEFORE timing, with a fixed (r, s): shard — the proof over all devices == the proof device 0
+    # computes alone with the whole key; throughput — the same proof from every device's replica.  (r, s) is drawn in every run, so
+    # that the timed steps draw the same blinders with and without --full.
     r_fix, s_fix = rand_fr(1)[0], rand_fr(1)[0]
-    if shard:
+    scale_parity = None
+    if args.full and shard:
         multi = mpk.prove_raw(zds, r_fix, s_fix, z_on_device=True)
         pk0 = groth16.ProvingKey(m.member(0), params, inst)
         single = pk0.prove_raw(zds[0], r_fix, s_fix, z_on_device=True)
@@ -302,11 +314,12 @@ def bench_single_process_multi(args):
         ok = bool(np.array_equal(multi[0], single[0]) and list(multi[1]) == list(single[1]))
         scale_parity = {"sharded_eq_single_gpu": ok, "ranks": n,
                         "note": "zkp_groth16_prove_multi over all devices vs zkp_groth16_prove_dev on device 0 with the full key"}
-    else:
+    elif args.full:
         outs, infs = mpk.prove_batch_raw(zds, np.stack([r_fix] * n), np.stack([s_fix] * n), z_on_device=True)
         ok = bool(all(np.array_equal(outs[k], outs[0]) and list(infs[k]) == list(infs[0]) for k in range(n)))
         scale_parity = {"all_devices_eq_device0": ok, "ranks": n, "note": "the same (z, r, s) proved once on every device's replica"}
-    log(f"scale_parity: {ok}")
+    if scale_parity is not None:
+        log(f"scale_parity: {ok}")
 
     steps(args.warmup)
     sync_all()
@@ -319,13 +332,14 @@ def bench_single_process_multi(args):
     proofs = args.steps if shard else args.steps * n
     # per-device roofline of the dominant kernel: device 0 alone with its own copy of the whole key (outside the timed region)
     roofline = None
-    try:
-        pk0 = groth16.ProvingKey(m.member(0), params, inst)
-        roofline, _ = accumulate_roofline(m.member(0), pk0, c, inst, lambda: pk0.prove_raw(zds[0], r_fix, s_fix, z_on_device=True), None)
-        roofline["from"] = "device 0 alone, whole key (per-device figure; the same kernel runs on every device)"
-        pk0.free()
-    except Exception as e:
-        log("per-device roofline failed:", repr(e))
+    if args.full:
+        try:
+            pk0 = groth16.ProvingKey(m.member(0), params, inst)
+            roofline, _ = accumulate_roofline(m.member(0), pk0, c, inst, lambda: pk0.prove_raw(zds[0], r_fix, s_fix, z_on_device=True), None)
+            roofline["from"] = "device 0 alone, whole key (per-device figure; the same kernel runs on every device)"
+            pk0.free()
+        except Exception as e:
+            log("per-device roofline failed:", repr(e))
     emit({
         "metric": "Groth16 proofs/sec (2^20 constraints, BN256)" if (args.log_n == 20 and c.name == "bn254" and not shard)
         else f"Groth16 proofs/sec (2^{args.log_n} domain, {c.name})" + (", ONE proof base-sharded over the GPUs" if shard else ""),
@@ -342,7 +356,7 @@ def bench_single_process_multi(args):
         "exchange": (dict(mpk.info(), call="inside zkp_groth16_prove_multi: ncclAllGather when the devices are distinct, else "
                                             "hipMemcpyPeerAsync (said on stderr); witness-map variant measured on proofs 3-4 of the key")
                      if shard else {"kind": "none (independent proofs, replicated key)", "devices": n}),
-        "roofline": roofline, "cpu_baseline": recorded_cpu_baseline(c.name, args.log_n)})
+        "roofline": roofline, "cpu_baseline": recorded_cpu_baseline(c.name, args.log_n) if args.full else None}, detail=args.full)
     for k, d in enumerate(zds):
         m.member(k).dev_free(d)
     mpk.free()
@@ -789,22 +803,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--log-n", type=int, default=20, help="QAP domain 2^k (k=20 is the BASELINE metric config)")
     ap.add_argument("--curve", default="bn254")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: CPU baseline, parity checks, rooflines, "
+                         "latency, the stand-alone MSM, Marlin and the other BASELINE configs (and write the full record to "
+                         "DETAIL_PATH).  Without it a run sets up, warms up, times the steps and prints the line.")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity check")
     ap.add_argument("--no-pipeline", action="store_true", help="one blocking zkp_groth16_prove_dev call per step")
     ap.add_argument("--mode", choices=["throughput", "shard"], default="throughput",
                     help="throughput (default, the BASELINE metric): independent proofs per GPU.  shard: ONE proof per step, every "
                          "query base-sharded over the ranks, partial sums all-gathered (RCCL) and folded — BASELINE configs[4]")
     ap.add_argument("--workload", choices=["groth16", "marlin"], default="groth16",
-                    help="groth16 (default, the BASELINE metric; its line also carries the other BASELINE configs as blocks "
-                         "unless --no-extra-configs / --no-marlin) or marlin: BASELINE configs[3] only")
-    ap.add_argument("--no-marlin", action="store_true")
+                    help="groth16 (default, the BASELINE metric; with --full its line also carries the other BASELINE configs as "
+                         "blocks unless --no-extra-configs / --no-marlin) or marlin: BASELINE configs[3] only")
+    ap.add_argument("--no-marlin", action="store_true", help="--full without the Marlin block")
     ap.add_argument("--no-extra-configs", action="store_true",
                     help="skip the blocks for BASELINE configs[2] (BLS12-381 2^22), configs[4] on one GPU (BN254 2^24) and the "
-                         "skewed-witness variant that the default N=1 BN254 2^20 line carries")
+                         "skewed-witness variant that the --full N=1 BN254 2^20 line carries")
     ap.add_argument("--extra", default="skewed,bls22,bn24", help="which extra blocks to run (comma-separated)")
-    ap.add_argument("--budget-s", type=float, default=1400.0,
-                    help="wall-clock budget of the whole run: an extra block is skipped (and says so) when the time already "
-                         "spent plus its estimate exceeds this")
+    ap.add_argument("--budget-s", type=float, default=540.0,
+                    help="wall-clock budget of a --full run: an extra block is skipped (and says so) when the time already "
+                         "spent plus its estimate exceeds this (the default keeps a --full run inside 10 minutes)")
     ap.add_argument("--devices", default="",
                     help="single-process multi-GPU only: comma-separated device ids for zkp_ctx_create_multi (default 0..gpus-1; "
                          "ids may repeat, e.g. 0,0,0 exercises the 3-rank path on a one-GPU box — not a multi-GPU measurement)")
@@ -846,14 +864,15 @@ def main():
     c = get_curve(args.curve)
     ctx = Context(local)
     if args.workload == "marlin":
-        m = bench_marlin(ctx, args.curve, reps=args.steps, cpu=not args.no_cpu_baseline, dump=args.dump_outputs)
+        m = bench_marlin(ctx, args.curve, reps=args.steps, verify=args.full, cpu=args.full and not args.no_cpu_baseline,
+                         dump=args.dump_outputs)
         if rank == 0:
             emit({"metric": "Marlin proofs/sec (2^20 constraints, BN256)", "value": m["value"], "unit": "proofs/s",
                               "n_gpus": 1, "steps": m["runs"], "warmup": 1, "ms_per_step": round(m["s_per_proof"] * 1e3, 2),
                               "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                               "dtype": "u32 limbs (256-bit Montgomery integers)", "data": "synthetic (MiMC-chain R1CS, trapdoor SRS)",
                               "config": {"workload": m["workload"]}, "roofline": m.pop("roofline"), "cpu_baseline": m.pop("cpu_baseline"),
-                              "marlin": m})
+                              "marlin": m}, detail=args.full)
         return
     t0 = time.time()
     S = samples_for_domain(args.log_n)
@@ -899,9 +918,9 @@ def main():
         outs, infs = pk.prove_batch_raw([z_dev] * k, rs[0], rs[1])
         return outs[-1], infs[-1]
 
-    # ---- N > 1: every rank proves the SAME (r, s) once before the timed region; the proofs must agree with rank 0's
+    # ---- N > 1, --full: every rank proves the SAME (r, s) once before the timed region; the proofs must agree with rank 0's
     scale_parity = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         fix = make_rand_fr(c, 99)
         p_out, p_inf = pk.prove_raw(z_dev, fix(), fix(), z_on_device=True)
@@ -930,6 +949,43 @@ def main():
 
     primary = args.log_n == 20 and c.name == "bn254"
     solo = rank == 0 and world == 1
+
+    def headline(table_plan):
+        """the record of a plain run; --full adds its blocks to it"""
+        return {
+            "metric": "Groth16 proofs/sec (2^20 constraints, BN256)" if primary
+            else f"Groth16 proofs/sec (2^{args.log_n} domain, {c.name})",
+            "value": round(args.steps * world / dt, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (256-bit Montgomery integers)",
+            "data": "synthetic (MiMC-chain R1CS, PRF witness, proving key generated from a fixed trapdoor)",
+            "config": {"workload": f"Groth16 prove, MiMC-chain R1CS, {inst.num_constraints()} constraints "
+                                   f"(domain 2^{args.log_n}), {inst.num_aux} aux, {c.name}, G1 x4 + G2 x1 MSM + 4 NTT (7 in the reference: evaluation-form key)",
+                       "curve": c.name, "log_domain": args.log_n, "parallelism": f"independent proofs x{world}",
+                       "table_plan": table_plan,
+                       "key_upload_s": key_upload_s,
+                       "key_form": "evaluation form unless ZKP_H_LAGRANGE=0 / ZKP_C_FOLD=0: H query transformed and C folded into the L "
+                                   "query once at upload (outside the timed region, like the window tables); 4 instead of 7 transforms per "
+                                   "proof, same proof bytes for every assignment (DESIGN.md section 5)",
+                       "pipelining": "none" if args.no_pipeline else f"{os.environ.get('ZKP_LANES', '8 (4 above 2^22)')} proofs in flight per GPU (zkp_groth16_prove_batch_dev), GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}"},
+            "scale_parity": scale_parity,
+            "exchange": None if world == 1 else {"kind": "none on the data path (independent proofs per rank, replicated key)",
+                                                 "control": ("gloo (TEST ONLY)" if args.single_device_test else "rccl") +
+                                                            ": barrier + max-over-ranks all_reduce" +
+                                                            (" + the scale_parity all_gather" if args.full else ""),
+                                                 "ranks": world}}
+
+    if not args.full:
+        if rank == 0:
+            emit(headline(pk.table_plan()), detail=False)
+            log(f"plain run: {time.time() - t_start:.1f} s from start to the line")
+        ctx.dev_free(z_dev)
+        pk.free()
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
+
     # ---- single-proof latency: blocking zkp_groth16_prove_dev calls, one proof in flight (the latency-oriented stream plan)
     latency = None
     if rank == 0:
@@ -1075,34 +1131,15 @@ def main():
                 except Exception as e:
                     extra[key] = {"error": repr(e)}
     if rank == 0:
-        proofs = args.steps * world
-        out = {
-            "metric": "Groth16 proofs/sec (2^20 constraints, BN256)" if primary
-            else f"Groth16 proofs/sec (2^{args.log_n} domain, {c.name})",
-            "value": round(proofs / dt, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (256-bit Montgomery integers)",
-            "data": "synthetic (MiMC-chain R1CS, PRF witness, proving key generated from a fixed trapdoor)",
-            "config": {"workload": f"Groth16 prove, MiMC-chain R1CS, {inst.num_constraints()} constraints "
-                                   f"(domain 2^{args.log_n}), {inst.num_aux} aux, {c.name}, G1 x4 + G2 x1 MSM + 4 NTT (7 in the reference: evaluation-form key)",
-                       "curve": c.name, "log_domain": args.log_n, "parallelism": f"independent proofs x{world}",
-                       "table_plan": table_plan,
-                       "key_upload_s": key_upload_s,
-                       "key_form": "evaluation form unless ZKP_H_LAGRANGE=0 / ZKP_C_FOLD=0: H query transformed and C folded into the L "
-                                   "query once at upload (outside the timed region, like the window tables); 4 instead of 7 transforms per "
-                                   "proof, same proof bytes for every assignment (DESIGN.md section 5)",
-                       "pipelining": "none" if args.no_pipeline else f"{os.environ.get('ZKP_LANES', '8 (4 above 2^22)')} proofs in flight per GPU (zkp_groth16_prove_batch_dev), GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}"},
+        out = headline(table_plan)
+        out.update({
             "roofline": roofline, "cpu_baseline": cpu_baseline if world == 1 else recorded_cpu_baseline(c.name, args.log_n),
             "hbm_peak_measured": hbm_meas,
             "roofline_ntt": roofline_ntt, "roofline_scan": roofline_scan, "valu_roof": valu_roof,
-            "with_h2d": with_h2d, "latency": latency, "parity_check": parity_check, "scale_parity": scale_parity,
-            "exchange": None if world == 1 else {"kind": "none on the data path (independent proofs per rank, replicated key)",
-                                                 "control": ("gloo (TEST ONLY)" if args.single_device_test else "rccl") +
-                                                            ": barrier + max-over-ranks all_reduce + the scale_parity all_gather",
-                                                 "ranks": world},
+            "with_h2d": with_h2d, "latency": latency, "parity_check": parity_check,
             "msm_g1": msm_g1, "marlin_config4": marlin, **extra,
             "phases_ms": phases, "bench_wall_s": round(time.time() - t_start, 1),
-        }
+        })
         out["summary"] = summary_block(out, marlin, extra)     # LAST key: the driver keeps the tail of the line
         emit(out)
     if world > 1:

@@ -166,3 +166,33 @@ def test_steps_is_the_number_of_timed_steps(monkeypatch, argv, want_steps):
     with pytest.raises(_Stop):
         b.main()
     assert seen["steps"] == want_steps and seen["dump"] == ("out" if "--dump-outputs" in argv else None)
+
+
+def test_a_plain_run_writes_no_detail_file(tmp_path, monkeypatch, capsys):
+    b = load_bench()
+    monkeypatch.chdir(tmp_path)
+    head = {"metric": "m", "value": 2.5, "unit": "proofs/s", "n_gpus": 1, "steps": 3, "warmup": 1, "ms_per_step": 400.0,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "d", "config": {"workload": "w"}}
+    b.emit(head, detail=False)
+    line = json.loads(capsys.readouterr().out)
+    assert line["value"] == 2.5 and line["ms_per_step"] == 400.0 and line["detail"] is None
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert list(tmp_path.iterdir()) == []
+
+
+@pytest.mark.parametrize("argv, want_full", [(["--gpus", "8"], False), (["--gpus", "8", "--full"], True)])
+def test_full_is_off_by_default(monkeypatch, argv, want_full):
+    b = load_bench()
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    seen = {}
+
+    def spy(args):
+        seen.update(full=args.full)
+        raise _Stop()
+
+    monkeypatch.setattr(b, "bench_single_process_multi", spy)
+    with pytest.raises(_Stop):
+        b.main()
+    assert seen["full"] is want_full

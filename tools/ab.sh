@@ -9,7 +9,7 @@ for V in "$@"; do
   python -m pytest tests/test_gpu_msm.py tests/test_gpu_groth16.py -x -q -m gpu -k "edge or known_dlog or mini or mimc_chain or exceptional or long_buckets" > $OUT/$V.test.log 2>&1
   T=$(tail -1 $OUT/$V.test.log)
   for i in 1 2; do
-    python bench.py --no-cpu-baseline --no-marlin ${AB_BENCH_ARGS:-} > $OUT/$V.bench$i.json 2> $OUT/$V.bench$i.err
+    python bench.py --full --no-cpu-baseline --no-marlin ${AB_BENCH_ARGS:-} > $OUT/$V.bench$i.json 2> $OUT/$V.bench$i.err
   done
   python - "$V" "$T" $OUT/$V.bench1.json $OUT/$V.bench2.json <<'PY'
 import json, sys

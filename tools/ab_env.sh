@@ -8,7 +8,7 @@ for pass in $(seq 1 $P); do
     export $VAR=$v
     s=$(SWEEP_ONLY_DEFAULT=1 python tools/msm_window_sweep.py bn254 20 2>/dev/null | awk '$1=="default"{print $3, $5}')
     m=$(python bench.py --workload marlin --no-cpu-baseline --steps 8 2>/dev/null | val)
-    g=$(python bench.py --no-cpu-baseline --no-marlin --no-extra-configs --steps 64 --warmup 10 2>/dev/null | val)
+    g=$(python bench.py --full --no-cpu-baseline --no-marlin --no-extra-configs --steps 64 --warmup 10 2>/dev/null | val)
     echo "pass $pass $VAR=$v  lone MSM 2^20 (median ms, Mop/s): $s   marlin (proofs/s ms -): $m   groth16 2^20 (proofs/s ms latency_ms): $g"
   done
 done

@@ -11,7 +11,7 @@ for i in $(seq 1 $R); do
   for E in "${VARS[@]}"; do
     k=$((k+1))
     if [ "$E" = "-" ]; then EE=""; else EE="$E"; fi
-    env $EE python bench.py --no-cpu-baseline --no-marlin --no-extra-configs "$@" > $OUT/v$k.$i.json 2> $OUT/v$k.$i.err
+    env $EE python bench.py --full --no-cpu-baseline --no-marlin --no-extra-configs "$@" > $OUT/v$k.$i.json 2> $OUT/v$k.$i.err
     python - "v$k[$E]" $OUT/v$k.$i.json <<'PY'
 import json, sys
 try:

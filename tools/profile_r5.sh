@@ -15,14 +15,14 @@ WIN=66 bash tools/trace_marlin.sh gpurun_out/prof_${R}_marlin > $O/trace_marlin_
 export TMPDIR=/tmp
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C -d $O/prof_${R}_marlin/pmc_$C -o pmc -- python $ROOT/bench.py --workload marlin --no-cpu-baseline --steps 1 > $O/prof_${R}_marlin/pmc_$C.json 2> $O/prof_${R}_marlin/pmc_$C.err
+  rocprofv3 --kernel-trace --pmc $C -d $O/prof_${R}_marlin/pmc_$C -o pmc -- python $ROOT/bench.py --full --workload marlin --no-cpu-baseline --steps 1 > $O/prof_${R}_marlin/pmc_$C.json 2> $O/prof_${R}_marlin/pmc_$C.err
   DB=$(find $O/prof_${R}_marlin/pmc_$C -name "*.db" | head -1)
   python $ROOT/tools/rocpd_pmc.py $DB accumulate > $O/prof_${R}_marlin/pmc_$C.txt 2>&1
   find $O/prof_${R}_marlin/pmc_$C -name "*.db" -delete
   find $O/prof_${R}_marlin/pmc_$C -name "*.csv" -size +1M -delete
 done
 cd $ROOT
-python bench.py > $O/bench_full.json 2> $O/bench_full.err
+python bench.py --full > $O/bench_full.json 2> $O/bench_full.err
 python bench.py --steps 20 --warmup 5 --no-marlin --no-extra-configs > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err
-python bench.py --workload marlin > $O/marlin.json 2> $O/marlin.err
+python bench.py --full --workload marlin > $O/marlin.json 2> $O/marlin.err
 for f in bench_full bench_driver_flags marlin; do echo $f; tail -1 $O/$f.json | tail -c 900; echo; done

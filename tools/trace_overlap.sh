@@ -6,7 +6,7 @@ ROOT=$PWD
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace -d $OUT/trace -o t -- python $ROOT/bench.py --no-cpu-baseline --no-marlin --steps 48 --warmup 8 "$@" > $OUT/trace_bench.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace -d $OUT/trace -o t -- python $ROOT/bench.py --full --no-cpu-baseline --no-marlin --steps 48 --warmup 8 "$@" > $OUT/trace_bench.json 2> $OUT/trace.err
 cd $ROOT
 DB=$(find $OUT/trace -name "*.db" | head -1)
 python tools/rocpd_overlap.py $DB > $OUT/overlap.txt 2>&1
