@@ -9,6 +9,9 @@ from . import _lib
 from .params import CurveParams, get_curve
 
 NTT_FFT, NTT_IFFT, NTT_COSET_FFT, NTT_COSET_IFFT = 0, 1, 2, 3
+SC_EQ_AB_MINUS_C, SC_PROD2, SC_PROD3 = 0, 1, 2            # zkp_sumcheck_kind
+SC_ARITY = {SC_EQ_AB_MINUS_C: 4, SC_PROD2: 2, SC_PROD3: 3}
+SC_POINTS = {SC_EQ_AB_MINUS_C: 3, SC_PROD2: 2, SC_PROD3: 3}
 
 
 def _ptr(a):
@@ -240,6 +243,39 @@ class Context:
         na = (C.c_size_t * max(k, 1))(*[int(n) for n in ns])
         _lib.check(self.lib.zkp_fr_dot_batch_dev(self.h, get_curve(curve).cid, k, aa, ba, na, _ptr(out)), "zkp_fr_dot_batch_dev")
         return out
+
+    def fr_sumcheck_round_dev(self, curve, kind: int, tables, length: int, bind=None, want_evals: bool = True):
+        """zkp_fr_sumcheck_round_dev over DEVICE tables of `length` Fr each (Montgomery): `tables` is the flat list of
+        count * arity(kind) pointers, term by term (SC_EQ_AB_MINUS_C: eq, a, b, c; SC_PROD2: a, b; SC_PROD3: a, b, c).
+        bind: one Montgomery Fr (4 x u64) bound into every distinct table first (length halves), or None.
+        Returns the (count, npoints) x 4 uint64 Montgomery evaluations g(0), g(2), (g(3)) per term, or None without want_evals."""
+        ar, npts = SC_ARITY[kind], SC_POINTS[kind]
+        assert len(tables) % ar == 0
+        count = len(tables) // ar
+        ta = (C.c_void_p * max(len(tables), 1))(*[p or None for p in tables])
+        x = None if bind is None else _c64(bind)
+        out = np.zeros((count, npts, 4), dtype=np.uint64) if want_evals else None
+        _lib.check(self.lib.zkp_fr_sumcheck_round_dev(self.h, get_curve(curve).cid, kind, count, ta, length, _ptr(x), _ptr(out)),
+                   "zkp_fr_sumcheck_round_dev")
+        return out
+
+    def fr_eq_evals_dev(self, curve, rs, out_ptr: int):
+        """zkp_fr_eq_evals_dev: the 2^k table of eq(., rs) into DEVICE memory; rs: (k, 4) uint64 Montgomery, rs[0] the top index bit."""
+        rs = _c64(rs).reshape(-1, 4)
+        _lib.check(self.lib.zkp_fr_eq_evals_dev(self.h, get_curve(curve).cid, _ptr(rs) if rs.shape[0] else None, rs.shape[0],
+                                                C.c_void_p(out_ptr or 0)), "zkp_fr_eq_evals_dev")
+
+    def fr_eq_evals(self, curve, rs) -> np.ndarray:
+        """Host convenience over fr_eq_evals_dev: (2^k, 4) uint64 Montgomery."""
+        rs = _c64(rs).reshape(-1, 4)
+        out = np.zeros((1 << rs.shape[0], 4), dtype=np.uint64)
+        d = self.dev_alloc(out.nbytes)
+        try:
+            self.fr_eq_evals_dev(curve, rs, d)
+            self.d2h(out, d)
+            return out
+        finally:
+            self.dev_free(d)
 
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)

@@ -8,6 +8,7 @@
 #include "host_field.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
+#include "sumcheck.hpp"
 
 using namespace zkp;
 
@@ -459,6 +460,15 @@ int32_t zkp_fr_dot_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, cons
                              const uint64_t* const* b_dev, const size_t* ns, uint64_t* out_host) {
   if (count && (!a_dev || !b_dev || !ns || !out_host)) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { fr_dot_batch(ctx, curve, count, a_dev, b_dev, ns, out_host); });
+}
+int32_t zkp_fr_sumcheck_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t kind, size_t count, uint64_t* const* tables_dev, size_t len,
+                                  const uint64_t* bind_host, uint64_t* evals_out_host) {
+  if ((count && !tables_dev) || (!bind_host && !evals_out_host)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_sumcheck_round(ctx, curve, kind, count, tables_dev, len, bind_host, evals_out_host); });
+}
+int32_t zkp_fr_eq_evals_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* r_host, size_t k, uint64_t* out_dev) {
+  if (!out_dev || (k && !r_host)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_eq_evals(ctx, curve, r_host, k, out_dev); });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

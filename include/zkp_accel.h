@@ -49,7 +49,8 @@ typedef struct zkp_ctx zkp_ctx; /* opaque: device, stream, twiddle tables, scrat
 
 const char* zkp_status_string(int32_t status);
 /* "zkp_accel <major.minor> (gfx950)".  0.7.1: zkp_g1_ipa_fold_dev (IPA generator fold) / zkp_fr_dot_batch_dev (batched Fr inner
- * products).  0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
+ * products); later in 0.7.1, detected by symbol: zkp_fr_sumcheck_round_dev (fused sum-check round) / zkp_fr_eq_evals_dev (eq
+ * table).  0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
  * watchdog (zkp_groth16_multi_info info[0] == 2); the multi-GPU entry points lock every member context.  0.5 (round 5): per-context lock (see Conventions); zkp_groth16_pk_upload_ex (ZKP_PK_KEEP_FORM); ZKP_MULTI_EXCHANGE=rccl also takes the RCCL
@@ -227,6 +228,35 @@ int32_t zkp_g1_ipa_fold_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_x
  * Every argument is checked before anything runs.  Returns after the results are on the host. */
 int32_t zkp_fr_dot_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* a_dev,
                              const uint64_t* const* b_dev, const size_t* ns, uint64_t* out_host);
+/* One sum-check round over dense multilinear tables of Fr (spartan/src/prover.rs:422-592, 594-723, 1442-1607): bind the previous
+ * challenge into every table (combine_with_r, polynomial.rs:130-138) and evaluate the next round polynomial of `count` terms at
+ * t = 0, 2, (3) (combine_with_n, polynomial.rs:121-128) in ONE pass over the tables plus one small launch that adds the
+ * per-workgroup partial sums.  g(1) is not computed: it is claim - g(0).
+ *   kind                    g                 tables per term (in this order)   points returned
+ *   ZKP_SC_EQ_AB_MINUS_C    eq (a b - c)      eq, a, b, c                       g(0), g(2), g(3)
+ *   ZKP_SC_PROD2            a b               a, b                              g(0), g(2)
+ *   ZKP_SC_PROD3            a b c             a, b, c                           g(0), g(2), g(3)
+ * tables_dev: count * arity(kind) device pointers (host array), each to len Fr (Montgomery, 16-byte aligned), len a power of two.
+ * bind_host != NULL: every DISTINCT table becomes combine_with_r(table, *bind_host) in place over [0, len/2), i.e.
+ *   t[j] = t[j] + x (t[j + len/2] - t[j]); elements [len/2, len) are left untouched; then len /= 2.
+ * evals_out_host != NULL: count * npoints(kind) Fr (Montgomery), term-major, of the (bound) tables:
+ *   g(t) = sum_{j < len/2} g(lo_j + t (hi_j - lo_j)) with lo_j = t[j], hi_j = t[j + len/2] per table.
+ * The same pointer may appear in several terms, or several times in one term: it is bound exactly once.
+ * ZKP_ERR_BAD_ARG: NULL or misaligned tables, len not a power of two or > 2^28, len < 2 with bind_host, a length below 2 at
+ * evaluation time, both bind_host and evals_out_host NULL, an unknown kind, *bind_host >= r, count > 256, two tables that overlap
+ * without being the same pointer.  Every argument is checked before anything runs: on an error nothing is written.
+ * Scratch: count * npoints(kind) * len / 16 bytes of partial sums (len / 32 with bind_host) from the context's grow-only arena;
+ * ZKP_ERR_OOM (nothing written) if the device cannot hold them, which only many terms over tables near 2^28 rows can reach.
+ * count == 0 -> ZKP_OK.  Runs on the context's current stream and returns after the evaluations are on the host.
+ * A proof of v rounds is v + 1 calls: (NULL, evals), then (r_{i-1}, evals) ..., then (r_{v-1}, NULL), which leaves the final
+ * values at element 0 of each table. */
+typedef enum { ZKP_SC_EQ_AB_MINUS_C = 0, ZKP_SC_PROD2 = 1, ZKP_SC_PROD3 = 2 } zkp_sumcheck_kind;
+int32_t zkp_fr_sumcheck_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t kind, size_t count, uint64_t* const* tables_dev,
+                                  size_t len, const uint64_t* bind_host, uint64_t* evals_out_host);
+/* eval_eq (spartan/src/polynomial.rs:8-24): out_dev[idx] = prod_i (bit_{k-1-i}(idx) ? r[i] : 1 - r[i]) for idx < 2^k, so r[0]
+ * decides the most significant bit of the index; k == 0 -> [1].  r_host: k Fr (Montgomery, each < r), host memory; out_dev: 2^k Fr
+ * (Montgomery, 16-byte aligned), device memory.  k > 28 or an r_host[i] >= r -> ZKP_ERR_BAD_ARG.  One launch. */
+int32_t zkp_fr_eq_evals_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* r_host, size_t k, uint64_t* out_dev);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
