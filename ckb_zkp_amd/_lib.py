@@ -153,6 +153,8 @@ SIGNATURES = {
     "zkp_fr_dot_batch_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, vp, vp, vp]),
     "zkp_fr_sumcheck_round_dev": (C.c_int32, [vp, C.c_int, C.c_int32, C.c_size_t, vp, C.c_size_t, vp, vp]),
     "zkp_fr_eq_evals_dev": (C.c_int32, [vp, C.c_int, vp, C.c_size_t, vp]),
+    "zkp_fr_product_circuit_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, C.c_size_t, vp]),
+    "zkp_fr_memcheck_circuits_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]),
     "zkp_msm_g1_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g2_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g1_mont_batch_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, vp, vp, vp]),

@@ -277,6 +277,30 @@ class Context:
         finally:
             self.dev_free(d)
 
+    def fr_product_circuit_dev(self, curve, circuits, n: int) -> np.ndarray:
+        """zkp_fr_product_circuit_dev: the layers above layer 0 of len(circuits) product circuits of n leaves each (DEVICE buffers
+        of 2n - 2 Fr, layer l at element 2n - (2n >> l)) -> the (count, 4) uint64 Montgomery roots."""
+        k = len(circuits)
+        roots = np.zeros((k, 4), dtype=np.uint64)
+        ca = (C.c_void_p * max(k, 1))(*[p or None for p in circuits])
+        _lib.check(self.lib.zkp_fr_product_circuit_dev(self.h, get_curve(curve).cid, k, ca, n, _ptr(roots)), "zkp_fr_product_circuit_dev")
+        return roots
+
+    def fr_memcheck_circuits_dev(self, curve, addrs, vals, tss, ts_add, circuits, n: int, gamma1, gamma2) -> np.ndarray:
+        """zkp_fr_memcheck_circuits_dev: leaf[i] = addr[i] gamma1^2 + val[i] gamma1 + ts[i] + ts_add - gamma2 as layer 0 of each
+        circuit, then the circuits.  addrs / tss: DEVICE pointers to n uint32 or None (addr[i] = i / ts[i] = 0); vals: DEVICE
+        pointers to n Montgomery Fr; ts_add: 0 or 1 per circuit; gamma1 / gamma2: one Montgomery Fr (4 x u64) each.
+        Returns the (count, 4) uint64 Montgomery roots."""
+        k = len(circuits)
+        assert len(addrs) == len(vals) == len(tss) == len(ts_add) == k
+        roots = np.zeros((k, 4), dtype=np.uint64)
+        arr = lambda ps: (C.c_void_p * max(k, 1))(*[p or None for p in ps])    # noqa: E731
+        ta = (C.c_uint32 * max(k, 1))(*[int(a) for a in ts_add])
+        _lib.check(self.lib.zkp_fr_memcheck_circuits_dev(self.h, get_curve(curve).cid, k, arr(addrs), arr(vals), arr(tss), ta,
+                                                         arr(circuits), n, _ptr(_c64(gamma1)), _ptr(_c64(gamma2)), _ptr(roots)),
+                   "zkp_fr_memcheck_circuits_dev")
+        return roots
+
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)
         xyz = _c64(xyz)

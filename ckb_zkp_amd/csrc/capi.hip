@@ -8,6 +8,7 @@
 #include "host_field.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
+#include "spark.hpp"
 #include "sumcheck.hpp"
 
 using namespace zkp;
@@ -469,6 +470,20 @@ int32_t zkp_fr_sumcheck_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t kind,
 int32_t zkp_fr_eq_evals_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* r_host, size_t k, uint64_t* out_dev) {
   if (!out_dev || (k && !r_host)) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { fr_eq_evals(ctx, curve, r_host, k, out_dev); });
+}
+int32_t zkp_fr_product_circuit_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, uint64_t* const* circuits_dev, size_t n,
+                                   uint64_t* roots_host) {
+  if (!circuits_dev || !roots_host) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_spark_circuits(ctx, curve, count, nullptr, nullptr, nullptr, nullptr, circuits_dev, n, nullptr, nullptr, roots_host); });
+}
+int32_t zkp_fr_memcheck_circuits_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint32_t* const* addr_dev,
+                                     const uint64_t* const* val_dev, const uint32_t* const* ts_dev, const uint32_t* ts_add,
+                                     uint64_t* const* circuits_dev, size_t n, const uint64_t* gamma1_host,
+                                     const uint64_t* gamma2_host, uint64_t* roots_host) {
+  if (!addr_dev || !val_dev || !ts_dev || !ts_add || !circuits_dev || !gamma1_host || !gamma2_host || !roots_host) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    fr_spark_circuits(ctx, curve, count, addr_dev, val_dev, ts_dev, ts_add, circuits_dev, n, gamma1_host, gamma2_host, roots_host);
+  });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

@@ -50,7 +50,8 @@ typedef struct zkp_ctx zkp_ctx; /* opaque: device, stream, twiddle tables, scrat
 const char* zkp_status_string(int32_t status);
 /* "zkp_accel <major.minor> (gfx950)".  0.7.1: zkp_g1_ipa_fold_dev (IPA generator fold) / zkp_fr_dot_batch_dev (batched Fr inner
  * products); later in 0.7.1, detected by symbol: zkp_fr_sumcheck_round_dev (fused sum-check round) / zkp_fr_eq_evals_dev (eq
- * table).  0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
+ * table), then zkp_fr_product_circuit_dev / zkp_fr_memcheck_circuits_dev (SPARK memory-checking hashes and product circuits).
+ * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
  * watchdog (zkp_groth16_multi_info info[0] == 2); the multi-GPU entry points lock every member context.  0.5 (round 5): per-context lock (see Conventions); zkp_groth16_pk_upload_ex (ZKP_PK_KEEP_FORM); ZKP_MULTI_EXCHANGE=rccl also takes the RCCL
@@ -257,6 +258,35 @@ int32_t zkp_fr_sumcheck_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t kind,
  * decides the most significant bit of the index; k == 0 -> [1].  r_host: k Fr (Montgomery, each < r), host memory; out_dev: 2^k Fr
  * (Montgomery, 16-byte aligned), device memory.  k > 28 or an r_host[i] >= r -> ZKP_ERR_BAD_ARG.  One launch. */
 int32_t zkp_fr_eq_evals_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* r_host, size_t k, uint64_t* out_dev);
+/* SPARK memory checking (later in 0.7.1, detected by symbol): the product circuits of `memory_checking` that
+ * product_circuit_eval_prover walks (spartan/src/spark.rs:209-347, prover.rs:1313-1440), every layer kept on the device.
+ *
+ * construct_product_circuit (spark.rs:315-347) for `count` circuits of n leaves each, layer 0 already in place.
+ * circuits_dev: count device pointers (host array); circuits_dev[k]: 2n - 2 Fr (Montgomery, canonical, 16-byte aligned).
+ * Layer l (n >> l elements, l = 0 .. log2 n - 1) starts at element 2n - (2n >> l); left_vec[l] / right_vec[l] of the reference are
+ * the first / second half of layer l:  layer[l+1][j] = layer[l][j] * layer[l][j + (n >> (l+1))].
+ * roots_host[k] (count Fr, Montgomery, host memory) = evaluate_product_circuit (spark.rs:349-359) = last layer's [0] * [1].
+ * n: a power of two, 2 <= n <= 2^28 (the reference's padding of odd lengths with 1 is never reached by Spartan's power-of-two tables
+ * and is not built); 1 <= count <= 256.  ZKP_ERR_BAD_ARG, before anything is launched or written: a NULL context or array, a NULL or
+ * misaligned circuits_dev[k], an n or count outside these rules, circuit buffers that overlap each other.
+ * Every element written is the canonical Montgomery representative (bit-exact results).  ceil((log2 n - 9) / 3) + 1 launches for
+ * n > 512, one below, whatever count is.  Runs on the context's current stream and returns after the roots are on the host. */
+int32_t zkp_fr_product_circuit_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, uint64_t* const* circuits_dev, size_t n,
+                                   uint64_t* roots_host);
+/* circuit_hash minus gamma2 (spark.rs:223-273, 298-312) written as layer 0 of circuit k, then the circuit as above:
+ *   leaf[i] = addr[i] * gamma1^2 + val[i] * gamma1 + (ts[i] + ts_add[k]) - gamma2
+ * addr_dev[k] == NULL: addr[i] = i (init / audit).  ts_dev[k] == NULL: ts[i] = 0 (init).  ts_add[k] is 0 or 1 (write = read + 1).
+ * addr_dev / val_dev / ts_dev / circuits_dev: host arrays of count device pointers; ts_add: count values, host memory.
+ * addr and ts are n uint32 each on the device, val is n Fr (Montgomery, 16-byte aligned).  gamma1_host / gamma2_host: one Fr each
+ * (Montgomery, < r), host memory.  Inputs may be shared between entries (the read and write circuits of a list share addr, val and
+ * ts: such a pair is hashed once); circuit buffers must not overlap each other or the inputs.
+ * ZKP_ERR_BAD_ARG, before anything is launched or written: the rules of zkp_fr_product_circuit_dev, a NULL or misaligned val_dev[k],
+ * a misaligned addr_dev[k] / ts_dev[k], ts_add[k] > 1, a gamma >= r, a circuit buffer that overlaps an input.
+ * The leaf pass is fused into the first launch: the launch count is that of zkp_fr_product_circuit_dev. */
+int32_t zkp_fr_memcheck_circuits_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint32_t* const* addr_dev,
+                                     const uint64_t* const* val_dev, const uint32_t* const* ts_dev, const uint32_t* ts_add,
+                                     uint64_t* const* circuits_dev, size_t n, const uint64_t* gamma1_host,
+                                     const uint64_t* gamma2_host, uint64_t* roots_host);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
