@@ -427,7 +427,7 @@ class Bases:
 
 
 # ---- Fr vector / polynomial primitives (device pointers), see include/zkp_accel.h
-VEC_MUL, VEC_ADD, VEC_SUB, VEC_SCALE, VEC_AXPY = 0, 1, 2, 3, 4
+VEC_MUL, VEC_ADD, VEC_SUB, VEC_SCALE, VEC_AXPY, VEC_ADDC = 0, 1, 2, 3, 4, 5     # the `op` of fr_vec_op
 
 
 def _ctx_method(fn):
@@ -492,9 +492,6 @@ def _bases_msm_mont_batch_dev(self, jobs) -> np.ndarray:
 
 
 Bases.msm_mont_batch_dev = _bases_msm_mont_batch_dev
-
-
-VEC_ADDC = 5
 
 
 @_ctx_method

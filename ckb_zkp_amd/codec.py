@@ -32,6 +32,16 @@ def fr_from_mont(a: np.ndarray, c: CurveParams) -> list:
     return [x * Ri % c.r for x in limbs_to_ints(a)]
 
 
+def fr_mont(x: int, c: CurveParams) -> np.ndarray:
+    """one integer -> (fr_limbs,) uint64 Montgomery"""
+    return fr_to_mont([x], c)[0]
+
+
+def fr_int(a: np.ndarray, c: CurveParams) -> int:
+    """one Montgomery element (fr_limbs u64 of any shape) -> integer"""
+    return fr_from_mont(a, c)[0]
+
+
 def fr_canonical(xs, c: CurveParams) -> np.ndarray:
     return ints_to_limbs([x % c.r for x in xs], c.fr_limbs)
 

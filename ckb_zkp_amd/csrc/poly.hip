@@ -14,7 +14,7 @@
 
 #include <vector>
 
-#include "field_dev.hpp"
+#include "fr_dev.hpp"
 #include "internal.hpp"
 
 namespace zkp {
@@ -244,7 +244,7 @@ static void poly_div_linear_t(zkp_ctx* ctx, const uint32_t* p, size_t n, const u
 void fr_vec_op(zkp_ctx* ctx, int curve, int op, const uint64_t* a, const uint64_t* b, const uint64_t* k_host,
                uint64_t* out, size_t n) {
   ZKP_REQUIRE(op >= 0 && op <= 5, ZKP_ERR_BAD_ARG);
-  uint32_t* kd = ctx->poly_consts.as<uint32_t>(128);
+  uint32_t* kd = PolyConsts::at(ctx, PolyConsts::Z);
   if (k_host) ZKP_HIP(hipMemcpyAsync(kd, k_host, 32, hipMemcpyHostToDevice, ctx->cur->stream));
   if (n == 0) return;
   auto launch = [&](auto tag) {
@@ -253,9 +253,7 @@ void fr_vec_op(zkp_ctx* ctx, int curve, int op, const uint64_t* a, const uint64_
                        reinterpret_cast<const uint32_t*>(a), reinterpret_cast<const uint32_t*>(b), kd,
                        reinterpret_cast<uint32_t*>(out), n, op);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 
@@ -270,18 +268,6 @@ struct DotDesc {
   uint32_t first_wg;           // entries without terms share first_wg with the next entry
 };
 template <class P>
-__device__ __forceinline__ Fp<P> dot_block_sum(Fp<P> acc, char* smem) {
-  using F = Fp<P>;
-  const int t = threadIdx.x;
-  acc.store(smem + t * 32);
-  __syncthreads();
-  for (int s = DOT_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) (F::load(smem + t * 32) + F::load(smem + (t + s) * 32)).store(smem + t * 32);
-    __syncthreads();
-  }
-  return F::load(smem);
-}
-template <class P>
 __global__ __launch_bounds__(DOT_THREADS) void dot_chunk_kernel(const DotDesc* __restrict__ descs, uint32_t count,
                                                                 uint32_t* __restrict__ partial) {
   using F = Fp<P>;
@@ -295,14 +281,14 @@ __global__ __launch_bounds__(DOT_THREADS) void dot_chunk_kernel(const DotDesc* _
   }
   const DotDesc d = descs[lo];
   const size_t base = (size_t)(wg - d.first_wg) * DOT_CHUNK;
-  F acc = F::zero();
+  F acc[1] = {F::zero()};
 #pragma unroll
   for (int k = 0; k < DOT_PER; k++) {
     const size_t i = base + (size_t)k * DOT_THREADS + threadIdx.x;
-    if (i < d.n) acc = acc + F::load(d.a + i * 8) * F::load(d.b + i * 8);
+    if (i < d.n) acc[0] = acc[0] + F::load(d.a + i * 8) * F::load(d.b + i * 8);
   }
-  acc = dot_block_sum<P>(acc, smem);
-  if (threadIdx.x == 0) acc.store(partial + (size_t)wg * 8);
+  fr_block_sum<F, DOT_THREADS, 1>(acc, smem);
+  if (threadIdx.x == 0) acc[0].store(partial + (size_t)wg * 8);
 }
 template <class P>
 __global__ __launch_bounds__(DOT_THREADS) void dot_final_kernel(const DotDesc* __restrict__ descs, const uint32_t* __restrict__ partial,
@@ -311,10 +297,10 @@ __global__ __launch_bounds__(DOT_THREADS) void dot_final_kernel(const DotDesc* _
   __shared__ __attribute__((aligned(16))) char smem[DOT_THREADS * 32];
   const DotDesc d = descs[blockIdx.x];
   const uint32_t chunks = (uint32_t)(((size_t)d.n + DOT_CHUNK - 1) / DOT_CHUNK);
-  F acc = F::zero();
-  for (uint32_t c = threadIdx.x; c < chunks; c += DOT_THREADS) acc = acc + F::load(partial + (size_t)(d.first_wg + c) * 8);
-  acc = dot_block_sum<P>(acc, smem);
-  if (threadIdx.x == 0) acc.store(out + (size_t)blockIdx.x * 8);
+  F acc[1] = {F::zero()};
+  for (uint32_t c = threadIdx.x; c < chunks; c += DOT_THREADS) acc[0] = acc[0] + F::load(partial + (size_t)(d.first_wg + c) * 8);
+  fr_block_sum<F, DOT_THREADS, 1>(acc, smem);
+  if (threadIdx.x == 0) acc[0].store(out + (size_t)blockIdx.x * 8);
 }
 
 void fr_dot_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* a, const uint64_t* const* b, const size_t* ns,
@@ -327,7 +313,8 @@ void fr_dot_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* 
     ZKP_REQUIRE(ns[k] <= ((size_t)1 << 31), ZKP_ERR_BAD_ARG);
     if (ns[k]) {
       ZKP_REQUIRE(a[k] && b[k], ZKP_ERR_BAD_ARG);
-      ZKP_REQUIRE((((uintptr_t)a[k] | (uintptr_t)b[k]) & 15) == 0, ZKP_ERR_BAD_ARG);     // 16-B vector loads
+      require_aligned16(a[k]);
+      require_aligned16(b[k]);
     }
     d[k] = {reinterpret_cast<const uint32_t*>(ns[k] ? a[k] : nullptr), reinterpret_cast<const uint32_t*>(ns[k] ? b[k] : nullptr),
             (uint32_t)ns[k], (uint32_t)total};
@@ -335,12 +322,12 @@ void fr_dot_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* 
     ZKP_REQUIRE(total < ((uint64_t)1 << 31), ZKP_ERR_BAD_ARG);
   }
   if (count == 0) return;
-  const size_t desc_bytes = (count * sizeof(DotDesc) + 255) & ~(size_t)255;
-  const size_t part_bytes = ((size_t)total * 32 + 255) & ~(size_t)255;
-  char* buf = reinterpret_cast<char*>(ctx->poly_tmp.get(desc_bytes + part_bytes + count * 32));
-  DotDesc* d_desc = reinterpret_cast<DotDesc*>(buf);
-  uint32_t* d_part = reinterpret_cast<uint32_t*>(buf + desc_bytes);
-  uint32_t* d_out = reinterpret_cast<uint32_t*>(buf + desc_bytes + part_bytes);
+  Scratch sc;
+  const size_t o_desc = sc.take(count * sizeof(DotDesc)), o_part = sc.take((size_t)total * 32), o_out = sc.take(count * 32);
+  sc.resolve(ctx->poly_tmp);
+  DotDesc* d_desc = sc.at<DotDesc>(o_desc);
+  uint32_t* d_part = sc.at<uint32_t>(o_part);
+  uint32_t* d_out = sc.at<uint32_t>(o_out);
   hipStream_t st = ctx->cur->stream;
   ZKP_HIP(hipMemcpyAsync(d_desc, d.data(), count * sizeof(DotDesc), hipMemcpyHostToDevice, st));
   auto launch = [&](auto tag) {
@@ -348,8 +335,7 @@ void fr_dot_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* 
     if (total) hipLaunchKernelGGL(dot_chunk_kernel<P>, dim3((uint32_t)total), dim3(DOT_THREADS), 0, st, d_desc, (uint32_t)count, d_part);
     hipLaunchKernelGGL(dot_final_kernel<P>, dim3((uint32_t)count), dim3(DOT_THREADS), 0, st, d_desc, d_part, d_out);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else launch(Bls381Fr{});
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipMemcpyAsync(out_host, d_out, count * 32, hipMemcpyDeviceToHost, st));
   ZKP_HIP(hipStreamSynchronize(st));
@@ -375,7 +361,7 @@ void marlin_round2_prod(zkp_ctx* ctx, int curve, const uint64_t* ra, const uint6
                         const uint64_t* z, const uint64_t* k_host, uint64_t* out, size_t n) {
   if (n == 0) return;
   hipStream_t st = ctx->cur->stream;
-  uint32_t* kd = ctx->poly_consts.as<uint32_t>(128) + 64;
+  uint32_t* kd = PolyConsts::at(ctx, PolyConsts::MARLIN);
   ZKP_HIP(hipMemcpyAsync(kd, k_host, 3 * 32, hipMemcpyHostToDevice, st));
   auto launch = [&](auto tag) {
     using P = decltype(tag);
@@ -383,9 +369,7 @@ void marlin_round2_prod(zkp_ctx* ctx, int curve, const uint64_t* ra, const uint6
                        reinterpret_cast<const uint32_t*>(za), reinterpret_cast<const uint32_t*>(zb), reinterpret_cast<const uint32_t*>(t),
                        reinterpret_cast<const uint32_t*>(z), (const uint32_t*)kd, reinterpret_cast<uint32_t*>(out), n);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 
@@ -441,7 +425,7 @@ __global__ __launch_bounds__(256) void marlin_t3_evals_kernel(MarlinOnK in, cons
 void marlin_t3_evals(zkp_ctx* ctx, int curve, const uint64_t* const* on_k, const uint64_t* k_host, uint64_t* out, size_t n) {
   if (n == 0) return;
   hipStream_t st = ctx->cur->stream;
-  uint32_t* kd = ctx->poly_consts.as<uint32_t>(128) + 64;
+  uint32_t* kd = PolyConsts::at(ctx, PolyConsts::MARLIN);
   ZKP_HIP(hipMemcpyAsync(kd, k_host, 5 * 32, hipMemcpyHostToDevice, st));
   MarlinOnK in;
   for (int j = 0; j < 9; j++) in.v[j] = reinterpret_cast<const uint32_t*>(on_k[j]);
@@ -451,9 +435,7 @@ void marlin_t3_evals(zkp_ctx* ctx, int curve, const uint64_t* const* on_k, const
     hipLaunchKernelGGL(marlin_t3_evals_kernel<P>, dim3((lanes + 255) / 256), dim3(256), 0, st, in, (const uint32_t*)kd,
                        reinterpret_cast<uint32_t*>(out), n, lanes);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 
@@ -486,7 +468,7 @@ void marlin_h2_numerator(zkp_ctx* ctx, int curve, const uint64_t* const* on_b, c
                          size_t n) {
   if (n == 0) return;
   hipStream_t st = ctx->cur->stream;
-  uint32_t* kd = ctx->poly_consts.as<uint32_t>(128) + 64;
+  uint32_t* kd = PolyConsts::at(ctx, PolyConsts::MARLIN);
   ZKP_HIP(hipMemcpyAsync(kd, k_host, 6 * 32, hipMemcpyHostToDevice, st));
   MarlinOnB in;
   for (int j = 0; j < 12; j++) in.v[j] = reinterpret_cast<const uint32_t*>(on_b[j]);
@@ -495,9 +477,7 @@ void marlin_h2_numerator(zkp_ctx* ctx, int curve, const uint64_t* const* on_b, c
     hipLaunchKernelGGL(marlin_h2_numerator_kernel<P>, dim3((n + 255) / 256), dim3(256), 0, st, in, reinterpret_cast<const uint32_t*>(t),
                        (const uint32_t*)kd, reinterpret_cast<uint32_t*>(out), n);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 
@@ -539,29 +519,16 @@ __global__ __launch_bounds__(256) void spmv_kernel(const uint32_t* __restrict__ 
 //   reduce:  one workgroup per row sums that row's partials.
 // Rows whose partial slots would not fit SPMV_PART_CAP are summed whole by their reduce workgroup.
 constexpr uint32_t SPMV_CHUNK = 8192, SPMV_PART_CAP = 1u << 16;
+constexpr int SPMV_THREADS = 256;                          // workgroup of the two long-row kernels
 template <class P>
-__device__ __forceinline__ Fp<P> block_sum(Fp<P> acc, uint32_t* red, uint32_t tid) {
-  using F = Fp<P>;
-  acc.store(red + tid * 8);
-  __syncthreads();
-  for (uint32_t s = 128; s > 0; s >>= 1) {
-    if (tid < s) {
-      acc = acc + F::load(red + (tid + s) * 8);
-      acc.store(red + tid * 8);
-    }
-    __syncthreads();
-  }
-  return acc;                                              // valid in lane 0
-}
-template <class P>
-__global__ __launch_bounds__(256) void spmv_long_partial_kernel(const uint32_t* __restrict__ row_ptr,
+__global__ __launch_bounds__(SPMV_THREADS) void spmv_long_partial_kernel(const uint32_t* __restrict__ row_ptr,
                                                                 const uint32_t* __restrict__ col,
                                                                 const uint32_t* __restrict__ coeff,
                                                                 const uint32_t* __restrict__ x,
                                                                 const uint32_t* __restrict__ long_list,
                                                                 uint32_t* __restrict__ partial) {
   using F = Fp<P>;
-  __shared__ uint32_t red[256 * 8];
+  __shared__ __attribute__((aligned(16))) char red[SPMV_THREADS * 32];
   const uint32_t count = min(long_list[0], SPMV_LIST_CAP), tid = threadIdx.x;
   const F one = F::one();
   uint32_t slot = 0;                                       // first partial slot of the current row
@@ -571,24 +538,23 @@ __global__ __launch_bounds__(256) void spmv_long_partial_kernel(const uint32_t* 
     if (slot + nch > SPMV_PART_CAP) break;                 // the rest is summed whole in the reduce kernel
     for (uint32_t c = blockIdx.x; c < nch; c += gridDim.x) {
       const uint32_t lo = b + c * SPMV_CHUNK, hi = min(e, lo + SPMV_CHUNK);
-      F acc = F::zero();
-      for (uint32_t k = lo + tid; k < hi; k += 256) acc = acc + spmv_term<P>(col, coeff, x, k, one);
-      acc = block_sum<P>(acc, red, tid);
-      if (tid == 0) acc.store(partial + (size_t)(slot + c) * 8);
-      __syncthreads();
+      F acc[1] = {F::zero()};
+      for (uint32_t k = lo + tid; k < hi; k += SPMV_THREADS) acc[0] = acc[0] + spmv_term<P>(col, coeff, x, k, one);
+      fr_block_sum<F, SPMV_THREADS, 1>(acc, red);
+      if (tid == 0) acc[0].store(partial + (size_t)(slot + c) * 8);
     }
     slot += nch;
   }
 }
 template <class P>
-__global__ __launch_bounds__(256) void spmv_long_reduce_kernel(const uint32_t* __restrict__ row_ptr,
+__global__ __launch_bounds__(SPMV_THREADS) void spmv_long_reduce_kernel(const uint32_t* __restrict__ row_ptr,
                                                                const uint32_t* __restrict__ col,
                                                                const uint32_t* __restrict__ coeff,
                                                                const uint32_t* __restrict__ x, uint32_t* __restrict__ out,
                                                                const uint32_t* __restrict__ long_list,
                                                                const uint32_t* __restrict__ partial) {
   using F = Fp<P>;
-  __shared__ uint32_t red[256 * 8];
+  __shared__ __attribute__((aligned(16))) char red[SPMV_THREADS * 32];
   const uint32_t count = min(long_list[0], SPMV_LIST_CAP), tid = threadIdx.x;
   const F one = F::one();
   uint32_t slot = 0;
@@ -598,15 +564,14 @@ __global__ __launch_bounds__(256) void spmv_long_reduce_kernel(const uint32_t* _
     const uint32_t nch = (e - b + SPMV_CHUNK - 1) / SPMV_CHUNK;
     fits = fits && (slot + nch <= SPMV_PART_CAP);
     if (r % gridDim.x == blockIdx.x) {
-      F acc = F::zero();
+      F acc[1] = {F::zero()};
       if (fits) {
-        for (uint32_t c = tid; c < nch; c += 256) acc = acc + F::load(partial + (size_t)(slot + c) * 8);
+        for (uint32_t c = tid; c < nch; c += SPMV_THREADS) acc[0] = acc[0] + F::load(partial + (size_t)(slot + c) * 8);
       } else {
-        for (uint32_t k = b + tid; k < e; k += 256) acc = acc + spmv_term<P>(col, coeff, x, k, one);
+        for (uint32_t k = b + tid; k < e; k += SPMV_THREADS) acc[0] = acc[0] + spmv_term<P>(col, coeff, x, k, one);
       }
-      acc = block_sum<P>(acc, red, tid);
-      if (tid == 0) acc.store(out + (size_t)i * 8);
-      __syncthreads();
+      fr_block_sum<F, SPMV_THREADS, 1>(acc, red);
+      if (tid == 0) acc[0].store(out + (size_t)i * 8);
     }
     if (fits) slot += nch;
   }
@@ -683,15 +648,13 @@ void fr_spmv(zkp_ctx* ctx, int curve, const uint32_t* row_ptr, const uint32_t* c
     hipLaunchKernelGGL(spmv_kernel<P>, dim3((nrows + 255) / 256), dim3(256), 0, st, row_ptr, col,
                        reinterpret_cast<const uint32_t*>(coeff), reinterpret_cast<const uint32_t*>(x), nrows,
                        reinterpret_cast<uint32_t*>(out), list);
-    hipLaunchKernelGGL(spmv_long_partial_kernel<P>, dim3(512), dim3(256), 0, st, row_ptr, col,
+    hipLaunchKernelGGL(spmv_long_partial_kernel<P>, dim3(512), dim3(SPMV_THREADS), 0, st, row_ptr, col,
                        reinterpret_cast<const uint32_t*>(coeff), reinterpret_cast<const uint32_t*>(x), list, partial);
-    hipLaunchKernelGGL(spmv_long_reduce_kernel<P>, dim3(256), dim3(256), 0, st, row_ptr, col,
+    hipLaunchKernelGGL(spmv_long_reduce_kernel<P>, dim3(256), dim3(SPMV_THREADS), 0, st, row_ptr, col,
                        reinterpret_cast<const uint32_t*>(coeff), reinterpret_cast<const uint32_t*>(x),
                        reinterpret_cast<uint32_t*>(out), list, partial);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 void fr_gather(zkp_ctx* ctx, const uint64_t* in, const int32_t* idx, size_t n, uint64_t* out) {
@@ -709,16 +672,14 @@ void poly_vanishing_fold(zkp_ctx* ctx, int curve, const uint64_t* p, size_t len,
     // division by (X - 1): blocked-scan Horner with z = 1, quotient and p(1) = the remainder in one go.
     auto go = [&](auto tag) {
       using P = decltype(tag);
-      uint32_t* zd = ctx->poly_consts.as<uint32_t>(128) + 32;           // (words 0..23 belong to fr_vec_op / poly_div_linear)
+      uint32_t* zd = PolyConsts::at(ctx, PolyConsts::VFOLD_ONE);
       uint32_t one[8];
       for (int i = 0; i < 8; i++) one[i] = P::ONE[i];
       ZKP_HIP(hipMemcpyAsync(zd, one, 32, hipMemcpyHostToDevice, st));   // pageable source: staged before the call returns
       poly_div_linear_t<P>(ctx, reinterpret_cast<const uint32_t*>(p), len, zd, reinterpret_cast<uint32_t*>(q),
                            reinterpret_cast<uint32_t*>(rem));
     };
-    if (curve == ZKP_BN254) go(Bn254Fr{});
-    else if (curve == ZKP_BLS12_381) go(Bls381Fr{});
-    else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+    with_fr(curve, go);
     return;
   }
   const size_t R = std::max<size_t>((len + n - 1) / n, 1);
@@ -740,9 +701,7 @@ void poly_vanishing_fold(zkp_ctx* ctx, int curve, const uint64_t* p, size_t len,
     hipLaunchKernelGGL(vfold_replay_kernel<P>, dim3((work + 255) / 256), dim3(256), 0, st, pp, len, n, C, T,
                        (const uint32_t*)carry, reinterpret_cast<uint32_t*>(q), reinterpret_cast<uint32_t*>(rem));
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 
@@ -754,9 +713,7 @@ void fr_batch_inverse(zkp_ctx* ctx, int curve, uint64_t* v, size_t n) {
     hipLaunchKernelGGL(batch_inverse_kernel<P>, dim3((lanes + 255) / 256), dim3(256), 0, ctx->cur->stream,
                        reinterpret_cast<uint32_t*>(v), n, lanes);
   };
-  if (curve == ZKP_BN254) launch(Bn254Fr{});
-  else if (curve == ZKP_BLS12_381) launch(Bls381Fr{});
-  else throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+  with_fr(curve, launch);
   ZKP_HIP(hipGetLastError());
 }
 
@@ -801,8 +758,7 @@ void poly_evaluate_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* 
       hipLaunchKernelGGL(horner_tile_batch_kernel<P>, dim3(max_tiles, jobs.size()), dim3(256), 0, st, jobs_dev);
       hipLaunchKernelGGL(horner_scan_batch_kernel<P>, dim3(1, jobs.size()), dim3(256), 0, st, jobs_dev);
     };
-    if (curve == ZKP_BN254) go(Bn254Fr{});
-    else go(Bls381Fr{});
+    with_fr(curve, go);
   }
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipMemcpyAsync(out_host, ev, 32 * count, hipMemcpyDeviceToHost, st));
@@ -812,17 +768,15 @@ void poly_evaluate_batch(zkp_ctx* ctx, int curve, size_t count, const uint64_t* 
 // q (n-1 coeffs, may be nullptr) = p / (X - z) ; eval_out (host, may be nullptr) = p(z)
 void poly_div_linear(zkp_ctx* ctx, int curve, const uint64_t* p, size_t n, const uint64_t* z_host, uint64_t* q,
                      uint64_t* eval_out_host) {
-  uint32_t* zd = ctx->poly_consts.as<uint32_t>(128);
+  uint32_t* zd = PolyConsts::at(ctx, PolyConsts::Z);
   ZKP_HIP(hipMemcpyAsync(zd, z_host, 32, hipMemcpyHostToDevice, ctx->cur->stream));
-  uint32_t* ev = zd + 16;
+  uint32_t* ev = PolyConsts::at(ctx, PolyConsts::DIV_EVAL);
   if (n == 0) {
     ZKP_HIP(hipMemsetAsync(ev, 0, 32, ctx->cur->stream));
-  } else if (curve == ZKP_BN254) {
-    poly_div_linear_t<Bn254Fr>(ctx, reinterpret_cast<const uint32_t*>(p), n, zd, reinterpret_cast<uint32_t*>(q), ev);
-  } else if (curve == ZKP_BLS12_381) {
-    poly_div_linear_t<Bls381Fr>(ctx, reinterpret_cast<const uint32_t*>(p), n, zd, reinterpret_cast<uint32_t*>(q), ev);
   } else {
-    throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
+    with_fr(curve, [&](auto tag) {
+      poly_div_linear_t<decltype(tag)>(ctx, reinterpret_cast<const uint32_t*>(p), n, zd, reinterpret_cast<uint32_t*>(q), ev);
+    });
   }
   if (eval_out_host) {
     ZKP_HIP(hipMemcpyAsync(eval_out_host, ev, 32, hipMemcpyDeviceToHost, ctx->cur->stream));

@@ -24,8 +24,7 @@
 #include <cstring>
 #include <vector>
 
-#include "field_dev.hpp"
-#include "host_field.hpp"
+#include "fr_dev.hpp"
 #include "spark.hpp"
 
 namespace zkp {
@@ -44,21 +43,10 @@ struct SpGroup {             // circuits that share their inputs: out[a] has ts_
 };
 
 template <class F>
-struct FrArg {               // one Fr element as a kernel argument
-  uint32_t v[F::N];
-};
-template <class F>
 struct SpConsts {
   FrArg<F> g1sq_r, g1, g2;   // gamma1^2 R (as a Montgomery word: gamma1^2 R^2), gamma1, gamma2
 };
 
-template <class F>
-__device__ __forceinline__ F sp_arg(const FrArg<F>& a) {
-  F x;
-#pragma unroll
-  for (int i = 0; i < F::N; i++) x.v[i] = a.v[i];
-  return x;
-}
 template <class F>
 __device__ __forceinline__ F sp_raw(uint32_t a) {          // the integer a as limbs: NOT Montgomery
   F x = F::zero();
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_pass_kernel(const SpGroup* __re
   if (j >= s) return;
   if (HASH) {
     const SpGroup g = groups[blockIdx.y];
-    const F g1sq_r = sp_arg(k.g1sq_r), g1 = sp_arg(k.g1), g2 = sp_arg(k.g2);
+    const F g1sq_r = k.g1sq_r.get(), g1 = k.g1.get(), g2 = k.g2.get();
     F base[R];
 #pragma unroll
     for (int i = 0; i < R; i++) base[i] = sp_leaf<F>(g, j + (size_t)i * s, g1sq_r, g1, g2);
@@ -137,7 +125,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_tail_kernel(const SpGroup* __re
   if (HASH) {
     g = groups[blockIdx.x];
     if (t < half) {
-      const F g1sq_r = sp_arg(k.g1sq_r), g1 = sp_arg(k.g1), g2 = sp_arg(k.g2);
+      const F g1sq_r = k.g1sq_r.get(), g1 = k.g1.get(), g2 = k.g2.get();
       a0 = sp_leaf<F>(g, t, g1sq_r, g1, g2);
       b0 = sp_leaf<F>(g, t + half, g1sq_r, g1, g2);
     }
@@ -183,15 +171,6 @@ __global__ __launch_bounds__(SP_THREADS) void sp_tail_kernel(const SpGroup* __re
   }
 }
 
-bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
-
-template <class P>
-FrArg<Fp<P>> fr_arg(const hostf::FrE& e) {
-  FrArg<Fp<P>> a;
-  memcpy(a.v, e.data(), 32);
-  return a;
-}
-
 template <class P, bool HASH>
 void launch_pass(hipStream_t st, int rl, dim3 grid, const SpGroup* groups, uint32_t* const* circ, size_t n, uint32_t l,
                  const SpConsts<Fp<P>>& k) {
@@ -206,12 +185,13 @@ void circuits_t(zkp_ctx* ctx, const std::vector<SpGroup>& groups, size_t count, 
                 const SpConsts<Fp<P>>& k, uint64_t* roots_host) {
   const bool hash = !groups.empty();
   hipStream_t st = ctx->cur->stream;
-  const size_t group_bytes = (groups.size() * sizeof(SpGroup) + 255) & ~(size_t)255;
-  const size_t circ_bytes = (count * sizeof(uint32_t*) + 255) & ~(size_t)255;
-  char* buf = reinterpret_cast<char*>(ctx->poly_tmp.get(group_bytes + circ_bytes + count * 32));
-  SpGroup* d_groups = reinterpret_cast<SpGroup*>(buf);
-  uint32_t** d_circ = reinterpret_cast<uint32_t**>(buf + group_bytes);
-  uint32_t* d_roots = reinterpret_cast<uint32_t*>(buf + group_bytes + circ_bytes);
+  Scratch sc;
+  const size_t o_groups = sc.take(groups.size() * sizeof(SpGroup)), o_circ = sc.take(count * sizeof(uint32_t*));
+  const size_t o_roots = sc.take(count * 32);
+  sc.resolve(ctx->poly_tmp);
+  SpGroup* d_groups = sc.at<SpGroup>(o_groups);
+  uint32_t** d_circ = sc.at<uint32_t*>(o_circ);
+  uint32_t* d_roots = sc.at<uint32_t>(o_roots);
   if (hash) ZKP_HIP(hipMemcpyAsync(d_groups, groups.data(), groups.size() * sizeof(SpGroup), hipMemcpyHostToDevice, st));
   ZKP_HIP(hipMemcpyAsync(d_circ, circuits, count * sizeof(uint32_t*), hipMemcpyHostToDevice, st));
 
@@ -257,8 +237,8 @@ void fr_spark_circuits(zkp_ctx* ctx, int curve, size_t count, const uint32_t* co
   hostf::FrE g1{}, g2{};
   if (hash) {
     ZKP_REQUIRE(addr_dev && ts_dev && ts_add && gamma1_host && gamma2_host, ZKP_ERR_BAD_ARG);
-    ZKP_REQUIRE(!fr.geq(reinterpret_cast<const uint32_t*>(gamma1_host)) && !fr.geq(reinterpret_cast<const uint32_t*>(gamma2_host)),
-                ZKP_ERR_BAD_ARG);
+    fr_require_canonical(curve, gamma1_host, 1);
+    fr_require_canonical(curve, gamma2_host, 1);
     memcpy(g1.data(), gamma1_host, 32);
     memcpy(g2.data(), gamma2_host, 32);
   }
@@ -268,11 +248,13 @@ void fr_spark_circuits(zkp_ctx* ctx, int curve, size_t count, const uint32_t* co
   spans.reserve(count * (hash ? 4 : 1));
   for (size_t i = 0; i < count; i++) {
     const uintptr_t c = (uintptr_t)circuits_dev[i];
-    ZKP_REQUIRE(c && (c & 15) == 0, ZKP_ERR_BAD_ARG);
+    ZKP_REQUIRE(c != 0, ZKP_ERR_BAD_ARG);
+    require_aligned16(circuits_dev[i]);
     spans.push_back({c, c + (2 * n - 2) * 32, true});
     if (!hash) continue;
     const uintptr_t v = (uintptr_t)val_dev[i], a = (uintptr_t)addr_dev[i], t = (uintptr_t)ts_dev[i];
-    ZKP_REQUIRE(v && (v & 15) == 0 && (a & 3) == 0 && (t & 3) == 0 && ts_add[i] <= 1, ZKP_ERR_BAD_ARG);
+    ZKP_REQUIRE(v && (a & 3) == 0 && (t & 3) == 0 && ts_add[i] <= 1, ZKP_ERR_BAD_ARG);
+    require_aligned16(val_dev[i]);
     spans.push_back({v, v + n * 32, false});
     if (a) spans.push_back({a, a + n * 4, false});
     if (t) spans.push_back({t, t + n * 4, false});
@@ -310,13 +292,10 @@ void fr_spark_circuits(zkp_ctx* ctx, int curve, size_t count, const uint32_t* co
   hostf::FrE r2e{};
   memcpy(r2e.data(), fr.r2, 32);
   const hostf::FrE g1sq_r = fr.mul(fr.mul(g1, g1), r2e);          // (gamma1^2 R) R: the Montgomery word of gamma1^2 R
-  if (curve == ZKP_BN254) {
-    const SpConsts<Fp<Bn254Fr>> k{fr_arg<Bn254Fr>(g1sq_r), fr_arg<Bn254Fr>(g1), fr_arg<Bn254Fr>(g2)};
-    circuits_t<Bn254Fr>(ctx, groups, count, circuits_dev, n, k, roots_host);
-  } else {
-    const SpConsts<Fp<Bls381Fr>> k{fr_arg<Bls381Fr>(g1sq_r), fr_arg<Bls381Fr>(g1), fr_arg<Bls381Fr>(g2)};
-    circuits_t<Bls381Fr>(ctx, groups, count, circuits_dev, n, k, roots_host);
-  }
+  with_fr(curve, [&](auto tag) {
+    using A = FrArg<Fp<decltype(tag)>>;
+    circuits_t<decltype(tag)>(ctx, groups, count, circuits_dev, n, {A(g1sq_r.data()), A(g1.data()), A(g2.data())}, roots_host);
+  });
 }
 
 }  // namespace zkp

@@ -11,7 +11,7 @@
 // slots of one term) share is bound by the first slot that reaches it in the thread's own order; the later ones read the two bound
 // values back (same thread, same addresses: program order).  Terms are spread over grid.y by groups that share no table.
 //
-// Reduction: an LDS tree per workgroup leaves one partial per (workgroup, term, point); sc_final_kernel (one workgroup per
+// Reduction: fr_block_sum (fr_dev.hpp) leaves one partial per (workgroup, term, point); sc_final_kernel (one workgroup per
 // (term, point)) adds them.  No hand-off between workgroups of one launch.  Field addition is exact: the order does not matter.
 //
 // Without a bind (round 0) the same kernel runs with one thread per j < len/2; a bind without evaluation (after the last round)
@@ -23,8 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "field_dev.hpp"
-#include "host_field.hpp"
+#include "fr_dev.hpp"
 #include "sumcheck.hpp"
 
 namespace zkp {
@@ -46,35 +45,6 @@ struct ScGroup {
   uint32_t first, n;         // terms [first, first + n) of the group-ordered term list
 };
 
-template <class F>
-struct FrArg {               // one Fr element as a kernel argument
-  uint32_t v[F::N];
-};
-
-// sums NP values per thread over the workgroup; thread 0 returns the totals in acc
-template <class F, int NP>
-__device__ __forceinline__ void sc_block_sum(F (&acc)[NP], char* smem) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int p = 0; p < NP; p++) acc[p].store(smem + (size_t)(p * SC_THREADS + t) * 32);
-  __syncthreads();
-  for (int s = SC_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int p = 0; p < NP; p++) {
-        char* a = smem + (size_t)(p * SC_THREADS + t) * 32;
-        (F::load(a) + F::load(a + (size_t)s * 32)).store(a);
-      }
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-#pragma unroll
-    for (int p = 0; p < NP; p++) acc[p] = F::load(smem + (size_t)p * SC_THREADS * 32);
-  }
-  __syncthreads();           // the next term reuses smem
-}
-
 // h threads along x: BIND ? len/4 : len/2.  Tables may alias each other (shared tables), so no pointer is __restrict__.
 template <class P, int KIND, bool BIND>
 __global__ __launch_bounds__(SC_THREADS) void sc_round_kernel(const ScTerm* terms, const ScGroup* groups, size_t h, FrArg<Fp<P>> xa,
@@ -85,9 +55,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_round_kernel(const ScTerm* term
   const size_t j = (size_t)blockIdx.x * SC_THREADS + threadIdx.x;
   const bool act = j < h;
   const ScGroup g = groups[blockIdx.y];
-  F x;
-#pragma unroll
-  for (int i = 0; i < F::N; i++) x.v[i] = xa.v[i];
+  const F x = xa.get();
   for (uint32_t k = 0; k < g.n; k++) {
     const ScTerm tm = terms[g.first + k];
     F e[NP];
@@ -127,7 +95,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_round_kernel(const ScTerm* term
         else e[p] = lo[0] * lo[1] * lo[2];
       }
     }
-    sc_block_sum<F, NP>(e, smem);
+    fr_block_sum<F, SC_THREADS, NP>(e, smem);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int p = 0; p < NP; p++) e[p].store(partial + ((size_t)(tm.out * NP + p) * gridDim.x + blockIdx.x) * 8);
@@ -143,7 +111,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_final_kernel(const uint32_t* __
   __shared__ __attribute__((aligned(16))) char smem[SC_THREADS * 32];
   F acc[1] = {F::zero()};
   for (uint32_t c = threadIdx.x; c < nwg; c += SC_THREADS) acc[0] = acc[0] + F::load(partial + ((size_t)blockIdx.x * nwg + c) * 8);
-  sc_block_sum<F, 1>(acc, smem);
+  fr_block_sum<F, SC_THREADS, 1>(acc, smem);
   if (threadIdx.x == 0) acc[0].store(out + (size_t)blockIdx.x * 8);
 }
 
@@ -153,9 +121,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_bind_kernel(uint32_t* const* __
   using F = Fp<P>;
   const size_t j = (size_t)blockIdx.x * SC_THREADS + threadIdx.x;
   if (j >= m) return;
-  F x;
-#pragma unroll
-  for (int i = 0; i < F::N; i++) x.v[i] = xa.v[i];
+  const F x = xa.get();
   uint32_t* t = tables[blockIdx.y];
   const F lo = F::load(t + j * 8);
   (lo + x * (F::load(t + (j + m) * 8) - lo)).store(t + j * 8);
@@ -189,21 +155,12 @@ __global__ __launch_bounds__(SC_THREADS) void sc_eq_kernel(const uint32_t* __res
   for (int a = 0; a < (1 << LOW); a++) e[a].store(out + ((t << LOW) + a) * 8);
 }
 
-bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
-
-template <class P>
-FrArg<Fp<P>> fr_arg(const uint64_t* host) {
-  FrArg<Fp<P>> a;
-  if (host) memcpy(a.v, host, 32);
-  else memset(a.v, 0, 32);
-  return a;
-}
-
 template <class P, int KIND>
 void launch_round(hipStream_t st, bool bind, dim3 grid, const ScTerm* terms, const ScGroup* groups, size_t h, const uint64_t* x,
                   uint32_t* partial) {
-  if (bind) hipLaunchKernelGGL((sc_round_kernel<P, KIND, true>), grid, dim3(SC_THREADS), 0, st, terms, groups, h, fr_arg<P>(x), partial);
-  else hipLaunchKernelGGL((sc_round_kernel<P, KIND, false>), grid, dim3(SC_THREADS), 0, st, terms, groups, h, fr_arg<P>(x), partial);
+  const FrArg<Fp<P>> xa(x);
+  if (bind) hipLaunchKernelGGL((sc_round_kernel<P, KIND, true>), grid, dim3(SC_THREADS), 0, st, terms, groups, h, xa, partial);
+  else hipLaunchKernelGGL((sc_round_kernel<P, KIND, false>), grid, dim3(SC_THREADS), 0, st, terms, groups, h, xa, partial);
 }
 
 template <class P>
@@ -214,7 +171,8 @@ void round_t(zkp_ctx* ctx, int kind, size_t count, uint64_t* const* tables, size
   // distinct tables, sorted by address: neighbours are the only candidates for an overlap (every table has len elements)
   std::vector<uintptr_t> uniq(slots);
   for (size_t i = 0; i < slots; i++) {
-    ZKP_REQUIRE(tables[i] && ((uintptr_t)tables[i] & 15) == 0, ZKP_ERR_BAD_ARG);
+    ZKP_REQUIRE(tables[i] != nullptr, ZKP_ERR_BAD_ARG);
+    require_aligned16(tables[i]);
     uniq[i] = (uintptr_t)tables[i];
   }
   std::sort(uniq.begin(), uniq.end());
@@ -228,7 +186,7 @@ void round_t(zkp_ctx* ctx, int kind, size_t count, uint64_t* const* tables, size
     uint32_t** d_tab = reinterpret_cast<uint32_t**>(ctx->poly_tmp.get(uniq.size() * sizeof(uint32_t*)));
     ZKP_HIP(hipMemcpyAsync(d_tab, uniq.data(), uniq.size() * sizeof(uint32_t*), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(sc_bind_kernel<P>, dim3((unsigned)((m + SC_THREADS - 1) / SC_THREADS), (unsigned)uniq.size()), dim3(SC_THREADS),
-                       0, st, d_tab, m, fr_arg<P>(bind_host));
+                       0, st, d_tab, m, FrArg<Fp<P>>(bind_host));
     ZKP_HIP(hipGetLastError());
     ZKP_HIP(hipStreamSynchronize(st));
     return;
@@ -271,17 +229,17 @@ void round_t(zkp_ctx* ctx, int kind, size_t count, uint64_t* const* tables, size
   const size_t h = bind_host ? len / 4 : len / 2;
   const uint32_t nwg = (uint32_t)((h + SC_THREADS - 1) / SC_THREADS);
   const size_t nout = count * np;
-  const size_t term_bytes = (count * sizeof(ScTerm) + 255) & ~(size_t)255;
-  const size_t group_bytes = (groups.size() * sizeof(ScGroup) + 255) & ~(size_t)255;
   // one partial per (workgroup, term, point): count * points * len / 16 (len / 32 with a bind) bytes, e.g. 6 MB for one fused
   // phase-one term of 2^26 rows.  Many terms over very long tables (256 terms of 2^28 rows: 13 GB) end as ZKP_ERR_OOM, as zkp_accel.h says.
   // A loop over several columns per thread would bound this, but took the fused kernel from 139 to 229 VGPRs (occupancy 3 -> 2).
-  const size_t part_bytes = nout * nwg * 32;
-  char* buf = reinterpret_cast<char*>(ctx->poly_tmp.get(term_bytes + group_bytes + part_bytes + nout * 32));
-  ScTerm* d_terms = reinterpret_cast<ScTerm*>(buf);
-  ScGroup* d_groups = reinterpret_cast<ScGroup*>(buf + term_bytes);
-  uint32_t* d_part = reinterpret_cast<uint32_t*>(buf + term_bytes + group_bytes);
-  uint32_t* d_out = reinterpret_cast<uint32_t*>(buf + term_bytes + group_bytes + part_bytes);
+  Scratch sc;
+  const size_t o_terms = sc.take(count * sizeof(ScTerm)), o_groups = sc.take(groups.size() * sizeof(ScGroup));
+  const size_t o_part = sc.take(nout * nwg * 32), o_out = sc.take(nout * 32);
+  sc.resolve(ctx->poly_tmp);
+  ScTerm* d_terms = sc.at<ScTerm>(o_terms);
+  ScGroup* d_groups = sc.at<ScGroup>(o_groups);
+  uint32_t* d_part = sc.at<uint32_t>(o_part);
+  uint32_t* d_out = sc.at<uint32_t>(o_out);
   ZKP_HIP(hipMemcpyAsync(d_terms, terms.data(), count * sizeof(ScTerm), hipMemcpyHostToDevice, st));
   ZKP_HIP(hipMemcpyAsync(d_groups, groups.data(), groups.size() * sizeof(ScGroup), hipMemcpyHostToDevice, st));
   const dim3 grid(nwg, (unsigned)groups.size());
@@ -321,21 +279,19 @@ void fr_sumcheck_round(zkp_ctx* ctx, int curve, int kind, size_t count, uint64_t
   ZKP_REQUIRE(is_pow2(len) && len <= ((size_t)1 << SC_MAX_LOG), ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(!bind_host || len >= 2, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(!evals_out_host || (bind_host ? len / 2 : len) >= 2, ZKP_ERR_BAD_ARG);   // the length at evaluation time
-  if (bind_host) ZKP_REQUIRE(!hostf::fr_field(curve).geq(reinterpret_cast<const uint32_t*>(bind_host)), ZKP_ERR_BAD_ARG);
+  if (bind_host) fr_require_canonical(curve, bind_host, 1);
   if (count == 0) return;
   ZKP_REQUIRE(tables != nullptr, ZKP_ERR_BAD_ARG);
-  if (curve == ZKP_BN254) round_t<Bn254Fr>(ctx, kind, count, tables, len, bind_host, evals_out_host);
-  else round_t<Bls381Fr>(ctx, kind, count, tables, len, bind_host, evals_out_host);
+  with_fr(curve, [&](auto tag) { round_t<decltype(tag)>(ctx, kind, count, tables, len, bind_host, evals_out_host); });
 }
 
 void fr_eq_evals(zkp_ctx* ctx, int curve, const uint64_t* r_host, size_t k, uint64_t* out_dev) {
   ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
   ZKP_REQUIRE(k <= (size_t)SC_MAX_LOG, ZKP_ERR_BAD_ARG);
-  ZKP_REQUIRE(out_dev && ((uintptr_t)out_dev & 15) == 0 && (k == 0 || r_host), ZKP_ERR_BAD_ARG);
-  const hostf::HostField fr = hostf::fr_field(curve);
-  for (size_t i = 0; i < k; i++) ZKP_REQUIRE(!fr.geq(reinterpret_cast<const uint32_t*>(r_host) + 8 * i), ZKP_ERR_BAD_ARG);
-  if (curve == ZKP_BN254) eq_t<Bn254Fr>(ctx, r_host, k, reinterpret_cast<uint32_t*>(out_dev));
-  else eq_t<Bls381Fr>(ctx, r_host, k, reinterpret_cast<uint32_t*>(out_dev));
+  ZKP_REQUIRE(out_dev && (k == 0 || r_host), ZKP_ERR_BAD_ARG);
+  require_aligned16(out_dev);
+  fr_require_canonical(curve, r_host, k);
+  with_fr(curve, [&](auto tag) { eq_t<decltype(tag)>(ctx, r_host, k, reinterpret_cast<uint32_t*>(out_dev)); });
 }
 
 }  // namespace zkp

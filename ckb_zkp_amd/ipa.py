@@ -15,18 +15,11 @@ from __future__ import annotations
 
 import numpy as np
 
+from .api import VEC_AXPY, VEC_SCALE
+from .codec import fr_int, fr_mont
 from .params import get_curve
 
-VEC_SCALE, VEC_AXPY = 3, 4
 MSM_SMALL_MAX_G1 = 1 << 16          # ZKP_MSM_SMALL_MAX_G1
-
-
-def _mont(x: int, r: int) -> np.ndarray:
-    return np.frombuffer(((x % r) * (1 << 256) % r).to_bytes(32, "little"), dtype=np.uint64).copy()
-
-
-def _int(a: np.ndarray, r: int) -> int:
-    return int.from_bytes(np.ascontiguousarray(a, dtype=np.uint64).tobytes(), "little") * pow(1 << 256, -1, r) % r
 
 
 def inner_product_prove(ctx, curve, g_xy, g_inf, q_xy, h_xy, a, b, gamma_blind, blinds, challenge):
@@ -57,7 +50,7 @@ def inner_product_prove(ctx, curve, g_xy, g_inf, q_xy, h_xy, a, b, gamma_blind, 
     try:
         dg, dgi, da, db, dqh = up(g_xy), up(g_flags), up(a), up(b), up(qh)
         ds = up(np.zeros((4, 4), dtype=np.uint64))            # [cl, blind_l, cr, blind_r] of the round
-        blind_fin = _int(gamma_blind, r)
+        blind_fin = fr_int(gamma_blind, c)
         l_vec, r_vec = [], []
         rnd = 0
         while n > 1:
@@ -89,20 +82,20 @@ def inner_product_prove(ctx, curve, g_xy, g_inf, q_xy, h_xy, a, b, gamma_blind, 
             x = challenge(l_xy, l_inf, r_xy, r_inf) % r
             assert x != 0
             xi = pow(x, -1, r)
-            xm, xim = _mont(x, r), _mont(xi, r)
+            xm, xim = fr_mont(x, c), fr_mont(xi, c)
             ctx.ipa_fold_dev(c, gl, gli, gr, gri, n, xim, xm, gl, gli)
             ctx.fr_vec_op(c, VEC_SCALE, al, None, al, n, xm)         # a' = x al + x^-1 ar
             ctx.fr_vec_op(c, VEC_AXPY, al, ar, al, n, xim)
             ctx.fr_vec_op(c, VEC_SCALE, bl, None, bl, n, xim)        # b' = x^-1 bl + x br
             ctx.fr_vec_op(c, VEC_AXPY, bl, br, bl, n, xm)
-            blind_fin = (blind_fin + x * x * _int(bl_, r) + xi * xi * _int(br_, r)) % r
+            blind_fin = (blind_fin + x * x * fr_int(bl_, c) + xi * xi * fr_int(br_, c)) % r
         a_fin, b_fin = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
         g_fin, g_fin_inf = np.zeros(w, dtype=np.uint64), np.zeros(1, dtype=np.uint8)
         ctx.d2h(a_fin, da)
         ctx.d2h(b_fin, db)
         ctx.d2h(g_fin, dg)
         ctx.d2h(g_fin_inf, dgi)
-        return l_vec, r_vec, a_fin, b_fin, (g_fin, bool(g_fin_inf[0])), _mont(blind_fin, r)
+        return l_vec, r_vec, a_fin, b_fin, (g_fin, bool(g_fin_inf[0])), fr_mont(blind_fin, c)
     finally:
         for p in bufs:
             ctx.dev_free(p)

@@ -17,10 +17,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from .api import VEC_MUL
+from .codec import fr_int, fr_mont
 from .params import get_curve
-from .sumcheck import _int, _mont, prove_cubic_batched
-
-VEC_MUL = 0
+from .sumcheck import prove_cubic_batched
 
 
 def layer_offset(n: int, l: int) -> int:
@@ -78,7 +78,7 @@ def memory_checking(ctx, curve, addrs_dev, mem_dev, read_ts_dev, audit_ts_dev, e
     r = c.r
     k = len(addrs_dev)
     assert k >= 1 and len(read_ts_dev) == k and len(e_dev) == k
-    g1, g2 = _mont(gamma[0], r), _mont(gamma[1], r)
+    g1, g2 = fr_mont(gamma[0], c), fr_mont(gamma[1], c)
     bufs = []
     try:
         for _ in range(2 * k):
@@ -90,8 +90,8 @@ def memory_checking(ctx, curve, addrs_dev, mem_dev, read_ts_dev, audit_ts_dev, e
         ops_roots = ctx.fr_memcheck_circuits_dev(c, rep(addrs_dev), rep(e_dev), rep(read_ts_dev), [0, 1] * k, ops, n, g1, g2)
         mem_roots = ctx.fr_memcheck_circuits_dev(c, [None, None], [mem_dev, mem_dev], [None, audit_ts_dev], [0, 0], [init, audit], m,
                                                  g1, g2)
-        roots = dict(init=_int(mem_roots[0], r), audit=_int(mem_roots[1], r), read=[_int(x, r) for x in ops_roots[0::2]],
-                     write=[_int(x, r) for x in ops_roots[1::2]])
+        roots = dict(init=fr_int(mem_roots[0], c), audit=fr_int(mem_roots[1], c), read=[fr_int(x, c) for x in ops_roots[0::2]],
+                     write=[fr_int(x, c) for x in ops_roots[1::2]])
         lhs, rhs = roots["init"], roots["audit"]
         for w, rd in zip(roots["write"], roots["read"]):
             lhs, rhs = lhs * w % r, rhs * rd % r
@@ -123,7 +123,7 @@ def product_circuit_eval_prover(ctx, curve, circuits, n: int, dotp, next_coeffs,
         top = np.zeros((2, 4), dtype=np.uint64)
         for p in circuits:
             ctx.d2h(top, p + 32 * layer_offset(n, layer_num - 1))
-            claims.append(_int(top[0], r) * _int(top[1], r) % r)
+            claims.append(fr_int(top[0], c) * fr_int(top[1], c) % r)
         d_eq = ctx.dev_alloc(32 * (n // 2))
         bufs.append(d_eq)
         layers, rands = [], []
@@ -132,7 +132,7 @@ def product_circuit_eval_prover(ctx, curve, circuits, n: int, dotp, next_coeffs,
             left_len = n >> (i + 1)
             lefts = [p + 32 * layer_offset(n, i) for p in circuits]
             par = [(lp, lp + 32 * left_len) for lp in lefts]
-            ctx.fr_eq_evals_dev(c, np.stack([_mont(x, r) for x in rands]) if rands else np.zeros((0, 4), np.uint64), d_eq)
+            ctx.fr_eq_evals_dev(c, np.stack([fr_mont(x, c) for x in rands]) if rands else np.zeros((0, 4), np.uint64), d_eq)
             with_dotp = i == 0 and len(dotp) > 0
             seq = []
             if with_dotp:
@@ -143,7 +143,7 @@ def product_circuit_eval_prover(ctx, curve, circuits, n: int, dotp, next_coeffs,
                 for (row, col, _), t in zip(seq, tmps):
                     ctx.fr_vec_op(c, VEC_MUL, row, col, t, left_len)
                 sums = ctx.fr_dot_batch_dev(c, tmps, [val for _, _, val in seq], [left_len] * len(seq))
-                claims = claims + [_int(s, r) for s in sums]
+                claims = claims + [fr_int(s, c) for s in sums]
             coeffs = [x % r for x in next_coeffs(len(claims))]
             claim = sum(x * w for x, w in zip(claims, coeffs)) % r
             polys, rand_prod, claim_prod, claim_dotp = prove_cubic_batched(ctx, c, par, d_eq, seq, coeffs, left_len, claim, next_round)

@@ -14,24 +14,15 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api import SC_EQ_AB_MINUS_C, SC_PROD2, SC_PROD3
+from .api import SC_EQ_AB_MINUS_C, SC_PROD2, SC_PROD3, VEC_AXPY, VEC_SCALE
+from .codec import fr_int, fr_mont
 from .params import get_curve
 
-VEC_SCALE, VEC_AXPY = 3, 4
 
-
-def _mont(x: int, r: int) -> np.ndarray:
-    return np.frombuffer(((x % r) * (1 << 256) % r).to_bytes(32, "little"), dtype=np.uint64).copy()
-
-
-def _int(a: np.ndarray, r: int) -> int:
-    return int.from_bytes(np.ascontiguousarray(a, dtype=np.uint64).tobytes(), "little") * pow(1 << 256, -1, r) % r
-
-
-def _first(ctx, ptr: int, r: int) -> int:
+def _first(ctx, ptr: int, c) -> int:
     a = np.zeros(4, dtype=np.uint64)
     ctx.d2h(a, ptr)
-    return _int(a, r)
+    return fr_int(a, c)
 
 
 def cubic_coeffs(e0: int, e2: int, e3: int, claim: int, r: int) -> list:
@@ -64,16 +55,16 @@ def _prove(ctx, c, kind, tables, n, claim, next_challenge, to_coeffs):
     length, x = n, None
     claim %= r
     for _ in range(n.bit_length() - 1):
-        ev = ctx.fr_sumcheck_round_dev(c, kind, tables, length, bind=None if x is None else _mont(x, r))
+        ev = ctx.fr_sumcheck_round_dev(c, kind, tables, length, bind=None if x is None else fr_mont(x, c))
         if x is not None:
             length //= 2
-        coeffs = to_coeffs([tuple(_int(p, r) for p in term) for term in ev], claim)
+        coeffs = to_coeffs([tuple(fr_int(p, c) for p in term) for term in ev], claim)
         x = next_challenge(list(coeffs)) % r
         claim = _evaluate(coeffs, x, r)
         polys.append(coeffs)
         rs.append(x)
     if x is not None:
-        ctx.fr_sumcheck_round_dev(c, kind, tables, length, bind=_mont(x, r), want_evals=False)
+        ctx.fr_sumcheck_round_dev(c, kind, tables, length, bind=fr_mont(x, c), want_evals=False)
     return polys, rs
 
 
@@ -82,14 +73,14 @@ def prove_phase_one(ctx, curve, d_eq, d_a, d_b, d_c, n, claim, next_challenge):
     c = get_curve(curve)
     polys, rx = _prove(ctx, c, SC_EQ_AB_MINUS_C, [d_eq, d_a, d_b, d_c], n, claim, next_challenge,
                        lambda ev, cl: cubic_coeffs(*ev[0], cl, c.r))
-    return polys, rx, tuple(_first(ctx, p, c.r) for p in (d_a, d_b, d_c, d_eq))
+    return polys, rx, tuple(_first(ctx, p, c) for p in (d_a, d_b, d_c, d_eq))
 
 
 def prove_phase_two(ctx, curve, d_abc, d_z, n, claim, next_challenge):
     """sum_check_proof_phase_two: g = abc z over DEVICE tables of n Fr.  Returns (polys, ry, (vs, vz))."""
     c = get_curve(curve)
     polys, ry = _prove(ctx, c, SC_PROD2, [d_abc, d_z], n, claim, next_challenge, lambda ev, cl: quadratic_coeffs(*ev[0], cl, c.r))
-    return polys, ry, tuple(_first(ctx, p, c.r) for p in (d_abc, d_z))
+    return polys, ry, tuple(_first(ctx, p, c) for p in (d_abc, d_z))
 
 
 def prove_cubic_batched(ctx, curve, par, c_par, seq, coeffs, n, claim, next_challenge):
@@ -106,7 +97,7 @@ def prove_cubic_batched(ctx, curve, par, c_par, seq, coeffs, n, claim, next_chal
         return cubic_coeffs(s[0], s[1], s[2], cl, r)
 
     polys, rs = _prove(ctx, c, SC_PROD3, tables, n, claim, next_challenge, to_coeffs)
-    f = lambda p: _first(ctx, p, r)                                # noqa: E731
+    f = lambda p: _first(ctx, p, c)                                # noqa: E731
     return (polys, rs, ([f(a) for a, _ in par], [f(b) for _, b in par], f(c_par) if par else None),
             ([f(a) for a, _, _ in seq], [f(b) for _, b, _ in seq], [f(t) for _, _, t in seq]))
 
@@ -164,12 +155,12 @@ def r1cs_sumcheck(ctx, curve, csr_a, csr_b, csr_c, z, tau, challenge_1, abc_chal
                 ctx.dev_zero(out, 32 * rows)
             d_abc.append(out)
         d_eq = alloc(32 * rows)
-        ctx.fr_eq_evals_dev(c, np.stack([_mont(t, r) for t in tau]).reshape(-1, 4) if len(tau) else np.zeros((0, 4), np.uint64), d_eq)
+        ctx.fr_eq_evals_dev(c, np.stack([fr_mont(t, c) for t in tau]).reshape(-1, 4) if len(tau) else np.zeros((0, 4), np.uint64), d_eq)
         polys_1, rx, vals = prove_phase_one(ctx, c, d_eq, *d_abc, rows, 0, challenge_1)
         va, vb, vc, _ = vals
         r_a, r_b, r_c = abc_challenges(*vals) if callable(abc_challenges) else abc_challenges
         # eq(rx), the three column products, their combination, then phase two against z
-        ctx.fr_eq_evals_dev(c, np.stack([_mont(t, r) for t in rx]).reshape(-1, 4) if rx else np.zeros((0, 4), np.uint64), d_eq)
+        ctx.fr_eq_evals_dev(c, np.stack([fr_mont(t, c) for t in rx]).reshape(-1, 4) if rx else np.zeros((0, 4), np.uint64), d_eq)
         d_cols = []
         for m in (csr_a, csr_b, csr_c):
             out = alloc(32 * nz)
@@ -179,9 +170,9 @@ def r1cs_sumcheck(ctx, curve, csr_a, csr_b, csr_c, z, tau, challenge_1, abc_chal
                 ctx.dev_zero(out, 32 * nz)
             d_cols.append(out)
         d_ev = d_cols[0]
-        ctx.fr_vec_op(c, VEC_SCALE, d_cols[0], None, d_ev, nz, _mont(r_a, r))
-        ctx.fr_vec_op(c, VEC_AXPY, d_ev, d_cols[1], d_ev, nz, _mont(r_b, r))
-        ctx.fr_vec_op(c, VEC_AXPY, d_ev, d_cols[2], d_ev, nz, _mont(r_c, r))
+        ctx.fr_vec_op(c, VEC_SCALE, d_cols[0], None, d_ev, nz, fr_mont(r_a, c))
+        ctx.fr_vec_op(c, VEC_AXPY, d_ev, d_cols[1], d_ev, nz, fr_mont(r_b, c))
+        ctx.fr_vec_op(c, VEC_AXPY, d_ev, d_cols[2], d_ev, nz, fr_mont(r_c, c))
         claim_2 = (r_a * va + r_b * vb + r_c * vc) % r
         polys_2, ry, vals_2 = prove_phase_two(ctx, c, d_ev, dz, nz, claim_2, challenge_2)
         return polys_1, rx, vals, polys_2, ry, vals_2

@@ -71,11 +71,13 @@ def test_marlin_prover_matches_oracle_and_verifies(ctx, curve, kind):
         ck.powers_of_gamma_g.free()
 
 
-def test_device_vector_primitives(ctx):
-    """spmv / gather / divide_by_vanishing / add-constant against plain big-int arithmetic."""
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
+def test_device_vector_primitives(ctx, curve):
+    """spmv / gather / divide_by_vanishing / add-constant against plain big-int arithmetic (both Fr fields: the long rows go
+    through the workgroup sum that every Fr-only unit shares)."""
     from ckb_zkp_amd import marlin as marlin_native
     from tests import marlin_pyorch as marlin_dev
-    c = get_curve("bn254")
+    c = get_curve(curve)
     rnd = random.Random(3)
     be = marlin_dev.DeviceBackend(ctx, c)
     try:
