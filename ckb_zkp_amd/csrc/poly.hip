@@ -21,10 +21,11 @@ namespace zkp {
 
 constexpr int POLY_CHUNK = 32;        // coefficients per lane
 
+// out may be a or b (zkp_accel.h; the sum-check, SPARK and Marlin drivers update vectors in place), so none of the three is
+// __restrict__: element i is read in full before it is written, and no thread touches another element.
 template <class P>
-__global__ __launch_bounds__(256) void vec_op_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
-                                                     const uint32_t* __restrict__ k, uint32_t* __restrict__ out,
-                                                     size_t n, int op) {
+__global__ __launch_bounds__(256) void vec_op_kernel(const uint32_t* a, const uint32_t* b, const uint32_t* __restrict__ k,
+                                                     uint32_t* out, size_t n, int op) {
   using F = Fp<P>;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

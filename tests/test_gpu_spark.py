@@ -123,7 +123,8 @@ def _ref_leaves(c, n, addr, val, ts, ts_add, g1, g2):
     return [(h - g2) % c.r for h in ref.circuit_hash(a, val, t, g1, c.r)]
 
 
-@pytest.mark.parametrize("n", [2, 8, 64, 1 << 11])
+# 2^10: the only length whose first launch is the radix-2 instance of the fused leaf pass
+@pytest.mark.parametrize("n", [2, 8, 64, 1 << 10, 1 << 11])
 @pytest.mark.parametrize("curve", CURVES)
 def test_memcheck_circuits(ctx, curve, n):
     c = get_curve(curve)
