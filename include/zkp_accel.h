@@ -112,7 +112,7 @@ int32_t zkp_timer_stop_ms(zkp_ctx* ctx, float* ms);
 
 /* ---- NTT: replaces ark-poly GeneralEvaluationDomain::<Fr> ops ----------------------------------
  * data: 2^log_n Fr elements (Montgomery), natural order in and out, in place.
- * log_n > TWO_ADICITY (28 BN254 / 32 BLS12-381) -> ZKP_ERR_DOMAIN_TOO_LARGE.
+ * log_n > 28 (BN254: its TWO_ADICITY) or > 30 (BLS12-381: TWO_ADICITY is 32, the library stops at 2^30) -> ZKP_ERR_DOMAIN_TOO_LARGE.
  * coset generator = Fr::multiplicative_generator() = 5 (BN254) / 7 (BLS12-381). */
 int32_t zkp_ntt(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* data_host, uint32_t log_n, int32_t op);
 int32_t zkp_ntt_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* data_dev, uint32_t log_n, int32_t op);
