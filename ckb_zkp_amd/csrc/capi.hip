@@ -50,21 +50,19 @@ int32_t guarded_multi(zkp_ctx* root, Fn&& fn) {
 
 zkp_cfg cfg_from_env() {
   zkp_cfg c;
-  auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-  auto off = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };
-  c.lanes = (int)num("ZKP_LANES", 0);
-  c.msm_batch_lanes = (int)std::max<long long>(1, std::min<long long>(num("ZKP_BATCH_LANES", 1), zkp_ctx::N_LANES));
-  c.msm_c = (int)num("ZKP_MSM_C", 0);
-  c.msm_c_g2 = (int)num("ZKP_MSM_C_G2", 0);
-  if (const char* e = getenv("ZKP_MSM_CHUNK")) c.msm_chunk = (long long)strtoull(e, nullptr, 0);
-  if (const char* e = getenv("ZKP_TABLE_BUDGET_GB")) c.table_budget_gb = atof(e);
-  c.h_lagrange = !off("ZKP_H_LAGRANGE");
-  c.c_fold = !off("ZKP_C_FOLD");
-  c.host_affine = !off("ZKP_HOST_AFFINE");
-  c.lfold_heavy_cost = num("ZKP_LFOLD_HEAVY_COST", c.lfold_heavy_cost);
-  if (const char* e = getenv("ZKP_MULTI_EXCHANGE")) c.multi_exchange = !strcmp(e, "rccl") ? ZKP_EXCHANGE_RCCL : !strcmp(e, "peer") ? ZKP_EXCHANGE_PEER : ZKP_EXCHANGE_AUTO;
-  c.multi_exchange_timeout_ms = (int)num("ZKP_MULTI_EXCHANGE_TIMEOUT_MS", c.multi_exchange_timeout_ms);
-  c.multi_wm_split = (int)num("ZKP_MULTI_WM_SPLIT", -1);
+  c.lanes = (int)env_num("ZKP_LANES", 0);
+  c.msm_batch_lanes = (int)std::max<long long>(1, std::min<long long>(env_num("ZKP_BATCH_LANES", 1), zkp_ctx::N_LANES));
+  c.msm_c = (int)env_num("ZKP_MSM_C", 0);
+  c.msm_c_g2 = (int)env_num("ZKP_MSM_C_G2", 0);
+  if (const char* e = env_str("ZKP_MSM_CHUNK")) c.msm_chunk = (long long)strtoull(e, nullptr, 0);
+  if (const char* e = env_str("ZKP_TABLE_BUDGET_GB")) c.table_budget_gb = atof(e);
+  c.h_lagrange = env_flag("ZKP_H_LAGRANGE", true);
+  c.c_fold = env_flag("ZKP_C_FOLD", true);
+  c.host_affine = env_flag("ZKP_HOST_AFFINE", true);
+  c.lfold_heavy_cost = env_num("ZKP_LFOLD_HEAVY_COST", c.lfold_heavy_cost);
+  if (const char* e = env_str("ZKP_MULTI_EXCHANGE")) c.multi_exchange = !strcmp(e, "rccl") ? ZKP_EXCHANGE_RCCL : !strcmp(e, "peer") ? ZKP_EXCHANGE_PEER : ZKP_EXCHANGE_AUTO;
+  c.multi_exchange_timeout_ms = (int)env_num("ZKP_MULTI_EXCHANGE_TIMEOUT_MS", c.multi_exchange_timeout_ms);
+  c.multi_wm_split = (int)env_num("ZKP_MULTI_WM_SPLIT", -1);
   return c;
 }
 
@@ -162,6 +160,7 @@ int32_t zkp_ctx_create_ex(zkp_ctx** out, int device_id, const zkp_ctx_config* us
   if (!ctx) return ZKP_ERR_OOM;
   ctx->device = device_id;
   ctx->cfg = cfg;
+  ctx->tune = tune_from_env();          // every context its own copy, members of a multi-device root included
   int32_t st = guarded(ctx, [&] {
     ZKP_HIP(hipEventCreate(&ctx->ev0));
     ZKP_HIP(hipEventCreate(&ctx->ev1));

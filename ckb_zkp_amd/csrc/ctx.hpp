@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/zkp_accel.h"
+#include "tune.hpp"
 
 namespace zkp {
 
@@ -125,9 +126,10 @@ struct zkp_lane {
   bool busy = false;
 };
 
-// Resolved per-context configuration (include/zkp_accel.h zkp_ctx_config): filled from the environment when the context is created
-// (the A/B variables stay the defaults), then overridden field by field by zkp_ctx_create_ex.  Read through ctx->cfg everywhere:
-// no prover switch is process-global.
+// Resolved per-context configuration (include/zkp_accel.h zkp_ctx_config): filled from the environment when the context is created,
+// then overridden field by field by zkp_ctx_create_ex.  cfg is the PUBLIC configuration; the internal A/B switches of the kernels and
+// schedules are zkp_tune (tune.hpp), filled from the environment at the same moment.  Both are per context and latched at creation:
+// read through ctx->cfg / ctx->tune everywhere, no prover switch is process-global.
 struct zkp_cfg {
   int lanes = 0;                      // 0: 8, 4 above 2^22 (groth16.hip prove_batch)
   int msm_batch_lanes = 1;
@@ -144,6 +146,7 @@ struct zkp_cfg {
 struct zkp_ctx {
   int device = 0;
   zkp_cfg cfg;
+  zkp_tune tune;
   // Every C-ABI entry point that takes this context holds this lock for the whole call (capi.hip guarded()): two host threads entering
   // ONE context are serialised instead of interleaving its lanes / scratch (since ABI 0.5; the documented contract stays "one ctx per
   // prover thread" — that is what runs concurrently).  Recursive: internal helpers may re-enter through a public entry point.
@@ -163,7 +166,7 @@ struct zkp_ctx {
   bool msm_defer_reduce = false;
   int msm_acc_into = -1;
   int msm_bucket_ws = -1;      // >= 0: the next MSM keeps its buckets in the bucket array of that workspace (chunked MSMs, msm.hip msm_run)
-  bool dbg_skip_k8 = false;    // ABLATION ONLY (ZKP_DEBUG_SKIP_K8_MASK): the next MSM skips its bucket reduction — wrong results, timing experiments
+  bool dbg_skip_k8 = false;    // ABLATION ONLY (tune.debug_skip_k8_mask): the next MSM skips its bucket reduction — wrong results, timing experiments
   bool batch_mode = false;     // inside zkp_groth16_prove_batch*: kernels are tuned for throughput of many proofs in flight, not latency
   std::map<std::pair<int, int>, zkp::NttTables> ntt_tables;   // (curve, log_n)
   zkp::DevBuf ntt_io, poly_tmp, poly_consts, spmv_list;

@@ -527,7 +527,7 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
       if (lagrange_on) shard_bounds(pk->N, rank, world, &hq_lo, &hq_n);
       const size_t ns[5] = {pk->q_n[0], pk->q_n[1], pk->q_n[2], lagrange_on ? hq_n : (world > 0 ? pk->q_n[3] : (size_t)d->h_len), pk->q_n[4]};
       lgk = bases_plan_lgk(ctx, d->curve, groups, ns, 5);
-      if (lgk > 0 && getenv("ZKP_DEBUG_MSM")) fprintf(stderr, "[groth16] window tables do not fit: window groups of %d\n", 1 << lgk);
+      if (lgk > 0 && env_str("ZKP_DEBUG_MSM")) fprintf(stderr, "[groth16] window tables do not fit: window groups of %d\n", 1 << lgk);
     }
     std::vector<uint8_t> fA, fB1, fB2, fL;
     pk->hA = upload_ext(ctx, d->curve, 1, d->a_query, d->a_inf, d->a_len, 2 * fq, tA, pk->q_lo[0], pk->q_n[0], 0, &fA, 0, 0, lgk);
@@ -542,17 +542,15 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
       // level-1 pass (one more digit scan per proof) and their accumulate kernels run 18-30 % longer instead of the 15 % more
       // entries: 139.2 (c = 17), 139.8 (c = 18), 137.2 (c = 16) vs 139.9 proofs/s with the shared configuration.  Off by
       // default; ZKP_B_WINDOW=1 enables it (ZKP_B_WINDOW_BITS / ZKP_B_TASK_CAP override the choice).
-      static const bool on = getenv("ZKP_B_WINDOW") && atoi(getenv("ZKP_B_WINDOW")) != 0;
       size_t live = 0;
       for (size_t i = 0; i < d->b_g2_len; i++) live += !(d->b_g2_inf && d->b_g2_inf[i]);
       int lg2 = 0;
       while (((size_t)2 << lg2) <= std::max<size_t>(live, 1)) lg2++;
       if (lg2 < 62 && (double)live >= 1.41421356 * (double)((size_t)1 << lg2)) lg2++;
-      if (on && world == 0 && live >= ((size_t)1 << 14) && !ctx->cfg.msm_c && !ctx->cfg.msm_c_g2) {
-        cB = std::max(12, std::min(20, lg2 - 2));
-        if (const char* e = getenv("ZKP_B_WINDOW_BITS")) cB = atoi(e);
-        capB = 32;
-        if (const char* e = getenv("ZKP_B_TASK_CAP")) capB = atoi(e);
+      const zkp_tune& tune = ctx->tune;                      // b_window_bits / b_task_cap: -1 = not given
+      if (tune.b_window && world == 0 && live >= ((size_t)1 << 14) && !ctx->cfg.msm_c && !ctx->cfg.msm_c_g2) {
+        cB = tune.b_window_bits >= 0 ? tune.b_window_bits : std::max(12, std::min(20, lg2 - 2));
+        capB = tune.b_task_cap >= 0 ? tune.b_task_cap : 32;
       }
     }
     pk->hB1 = upload_ext(ctx, d->curve, 1, d->b_g1_query, d->b_g1_inf, d->b_g1_len, 2 * fq, tB1, pk->q_lo[1], pk->q_n[1], 0, &fB1, cB, capB, lgk);
@@ -561,10 +559,9 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
       // B1 reuses B2's bucket sort + task schedule (same scalars, window configuration and identity pattern): -0.55 ms of
       // memory-bound sort kernels per proof.  With 4 hardware queues this LOST 2 % (84.7 -> 83.0 proofs/s: the wait on
       // B2's stream idled a queue); with 16 queues it gains 1-2 % (97.9 -> 99.3).  ZKP_SHARE_B_SORT=0 disables it.
-      static const bool on = !(getenv("ZKP_SHARE_B_SORT") && atoi(getenv("ZKP_SHARE_B_SORT")) == 0);
       const bool same_inf = (!d->b_g1_inf && !d->b_g2_inf) ||
                             (d->b_g1_inf && d->b_g2_inf && memcmp(d->b_g1_inf, d->b_g2_inf, d->b_g1_len) == 0);
-      pk->share_b_sort = on && same_inf && bases_same_shape(ctx, pk->hB1, pk->hB2);
+      pk->share_b_sort = ctx->tune.share_b_sort && same_inf && bases_same_shape(ctx, pk->hB1, pk->hB2);
     }
     if (lagrange_on) {
       LagrangeCache& cache = lagrange_cache;
@@ -612,7 +609,6 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
       // made both accumulate kernels 20 % longer (1.02 -> 1.25 ms) for one sort less, 122.2 vs 121.0 proofs/s and + 0.2 ms
       // single-proof latency — not taken: the limit is 1/16 of the bases.
       // ZKP_SHARE_AL_SORT=0 disables it.
-      static const bool on = !(getenv("ZKP_SHARE_AL_SORT") && atoi(getenv("ZKP_SHARE_AL_SORT")) == 0);
       bool same = fA.size() == fL.size() && pk->q_lo[0] == pk->q_lo[4];
       size_t differ = 0;
       std::vector<uint8_t> both(fA.size());
@@ -620,17 +616,16 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
         both[k] = fA[k] & fL[k];
         differ += fA[k] != fL[k];
       }
-      pk->share_al_sort = on && same && differ <= fA.size() / 16 && bases_same_shape(ctx, pk->hL, pk->hA) && pk->q_n[0] > 0;
+      pk->share_al_sort = ctx->tune.share_al_sort && same && differ <= fA.size() / 16 && bases_same_shape(ctx, pk->hL, pk->hA) && pk->q_n[0] > 0;
       if (pk->share_al_sort && differ) bases_set_sort_flags(ctx, pk->hA, both.data(), both.size());
       // One level-1 pass over z for A, B2 (whose sort B1 reuses) and L: the digit scan, the (bin, tile) counts and the scatter
       // into bins are done once, by A, over the bases that are NOT the identity in all three queries; every query then
       // runs its own level-2 sort and drops its own identities there (three flag bits in the top of every entry, bases_set_group), so
       // each accumulate kernel still sees exactly its own entries.  Two of the four digit scans of a proof disappear
       // (ZKP_SHARE_L1=0 disables it).
-      static const bool on_l1 = !(getenv("ZKP_SHARE_L1") && atoi(getenv("ZKP_SHARE_L1")) == 0);
       const bool aligned = fA.size() == fL.size() && fA.size() == fB2.size() && pk->q_lo[0] == pk->q_lo[4] &&
                            pk->q_lo[0] == pk->q_lo[2] && pk->q_n[0] > 0;
-      if (on_l1 && aligned && !pk->share_al_sort && bases_same_shape(ctx, pk->hL, pk->hA)) {
+      if (ctx->tune.share_l1 && aligned && !pk->share_al_sort && bases_same_shape(ctx, pk->hL, pk->hA)) {
         // (hB2 is a G2 table: same n, window configuration checked through hB1 / share_b_sort).  B queries with their own
         // window configuration (above) run their own level-1 pass: the group is then A and L only.
         const bool with_b = pk->share_b_sort && bases_same_shape(ctx, pk->hB1, pk->hA);
@@ -650,13 +645,12 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
       {
         // C only ever needs l' + h_acc (prover.rs:189-196): with equal bucket ranges and no window groups H's accumulate kernel
         // continues from L's finished buckets and ONE reduction yields the sum; L's own result is the identity (ZKP_CHAIN_LH=0: off)
-        static const bool on_chain = !(getenv("ZKP_CHAIN_LH") && atoi(getenv("ZKP_CHAIN_LH")) == 0);
         uint64_t iL[5], iH[5];
         bases_info(ctx, pk->hL, iL);
         bases_info(ctx, pk->hH, iH);
-        pk->chain_lh = on_chain && iL[0] == iH[0] && iL[2] == 1 && iH[2] == 1 && pk->q_n[3] > 0 && pk->q_n[4] > 0;
+        pk->chain_lh = ctx->tune.chain_lh && iL[0] == iH[0] && iL[2] == 1 && iH[2] == 1 && pk->q_n[3] > 0 && pk->q_n[4] > 0;
       }
-      if (getenv("ZKP_DEBUG_MSM"))
+      if (env_str("ZKP_DEBUG_MSM"))
         fprintf(stderr, "[groth16] A/L sort sharing: %d (flags differ at %zu of %zu bases), B1/B2: %d, shared level 1: %d\n",
                 (int)pk->share_al_sort, differ, fA.size(), (int)pk->share_b_sort, (int)pk->share_l1);
     }
@@ -730,8 +724,7 @@ static uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_
                        pk->m[k].coeff, z_dev, pk->num_constraints, N, pk->num_inputs, k == 0 ? 1 : 0, bufs[k]);
   // One launch for a, b, c (grid.y = 3) shortens the witness map in isolation (1.49 -> 1.35 ms at 2^20) but its 3x larger
   // launches delay the MSM streams of the other lane: 79 vs 85 proofs/s pipelined.  Off unless ZKP_NTT_BATCH=1.
-  static const bool batch = getenv("ZKP_NTT_BATCH") && atoi(getenv("ZKP_NTT_BATCH")) != 0;
-  if (batch) {
+  if (ctx->tune.ntt_batch) {
     ntt_run_batch(ctx, pk->curve, bufs, nchain, pk->log_n, ZKP_NTT_IFFT);
     ntt_run_batch(ctx, pk->curve, bufs, nchain, pk->log_n, ZKP_NTT_COSET_FFT);
   } else {
@@ -831,8 +824,8 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
   // Schedule.  profiling: everything on the main stream, one MSM at a time, with per-phase events.
   // otherwise: three streams —  main: witness_map -> H ;  ws1: A -> L ;  ws2: B1 -> B2  — joined before assembly.
   // ZKP_SINGLE_STREAM=1: one stream per proof (no fan-out inside a proof); concurrency then comes from the lanes only
-  static const bool single_stream = getenv("ZKP_SINGLE_STREAM") && atoi(getenv("ZKP_SINGLE_STREAM")) != 0;
-  const bool fan = !prof && !single_stream;
+  const zkp_tune& tune = ctx->tune;
+  const bool fan = !prof && !tune.single_stream;
   uint32_t* h = nullptr;
   auto run = [&](int idx, uint64_t handle, const uint64_t* sc, size_t n, int w, int sort_src = -1, int l1_src = -1) {
     float ms = 0.f, ms_sc = 0.f;
@@ -841,8 +834,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     ctx->tl_tag = names[idx];
     tic();
 #ifdef ZKP_ABLATION   // timing ablation builds only (ZKP_BUILD_DEFS=-DZKP_ABLATION -> variants/<tag>/): WRONG proofs, never in the shipped library
-    static const int skip_k8 = [] { const char* e = getenv("ZKP_DEBUG_SKIP_K8_MASK"); return e ? (int)strtol(e, nullptr, 0) : 0; }();
-    ctx->dbg_skip_k8 = ((skip_k8 >> idx) & 1) && ctx->batch_mode;
+    ctx->dbg_skip_k8 = ((tune.debug_skip_k8_mask >> idx) & 1) && ctx->batch_mode;
 #endif
     msm_run(ctx, handle, 0, sc, n, true, nullptr, res + idx * slot, prof ? &ms : nullptr, &e, fan ? w : 0,
             fan ? sort_src : -1, prof ? &ms_sc : nullptr, fan ? l1_src : -1);
@@ -868,8 +860,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     // the ~150 launches of the four other MSMs (0.5 ms of host time): single-proof latency 10.1 -> 9.65 ms (ZKP_WM_FIRST=0: after
     // them, as in round 1).  Making the other MSMs' accumulate kernels wait for it — a kernel timeline shows machine-filling
     // accumulates from three streams leaving its kernels few wave slots for milliseconds — was measured too: 10.3 ms, not kept.
-    static const bool wm_first = !(getenv("ZKP_WM_FIRST") && atoi(getenv("ZKP_WM_FIRST")) == 0);
-    if (wm_first) {
+    if (tune.wm_first) {
       h = witness_map_dev<FrP>(ctx, pk, S, !pk->h_lagrange);
       ctx->mark(st, "wm");
     }
@@ -879,10 +870,9 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     //  machine-filling accumulates only change places; what ends last is still one accumulate + its reduction.  A third plan — main: map ->
     //  H (sorted, accumulated, reduction deferred) -> L on top of H's buckets; B2 at once; A / B1 accumulates held until H is sorted —
     //  proved correct and ran 9.2-9.7 ms.  profiles/r04_latency_experiments.txt.)
-    static const bool l_own = !(getenv("ZKP_L_OWN_STREAM") && atoi(getenv("ZKP_L_OWN_STREAM")) == 0);
-    static const int lat_env = [] { const char* e = getenv("ZKP_LATENCY_PLAN"); return e ? atoi(e) : -1; }();
+    const bool l_own = tune.l_own_stream;
     (void)latency_plan;
-    const bool lat = lat_env >= 0 ? lat_env != 0 : true;
+    const bool lat = tune.latency_plan >= 0 ? tune.latency_plan != 0 : true;
     if (lat) {
       // Stream plan (round 2; default for single proofs AND the pipelined batch — measured 113.6 vs 111.2 proofs/s and 11.0 vs
       // 11.9 ms single-proof latency against the round-1 plan below, which ZKP_LATENCY_PLAN=0 restores):
@@ -895,8 +885,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
       ZKP_HIP(hipEventRecord(ctx->cur->ev_a, ctx->cur->ws[1].stream));
       if (b_l1) run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 2, -1, l1);
       // proof.b needs B2 only: its into_affine runs on B2's stream as soon as the MSM is done instead of in the tail of the proof
-      static const bool g2_early = !(getenv("ZKP_G2_EARLY") && atoi(getenv("ZKP_G2_EARLY")) == 0);
-      if (!partial_out && g2_early && !host_tail) {
+      if (!partial_out && tune.g2_early && !host_tail) {
         v2->assemble_g2(ctx->cur->ws[2].stream, res, slot, proof_dev, flags_dev, 2 * v1->fN);
         g2_done_in_fan = true;
       }
@@ -1014,9 +1003,7 @@ static std::vector<const void*> lane_signature(zkp_ctx* ctx, zkp_groth16_pk* pk)
 template <class FrP>
 static void prove_enqueue(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
                           const uint64_t* s, bool latency_plan = false) {
-  static const bool graph_on = getenv("ZKP_GRAPH") && atoi(getenv("ZKP_GRAPH")) != 0;
-  static const bool single_stream = getenv("ZKP_SINGLE_STREAM") && atoi(getenv("ZKP_SINGLE_STREAM")) != 0;
-  if (!graph_on || ctx->profiling || single_stream) {
+  if (!ctx->tune.graph || ctx->profiling || ctx->tune.single_stream) {
     prove_enqueue_part<FrP>(ctx, pk, z, z_on_device, r, s, 3, nullptr, latency_plan);
     return;
   }
@@ -1171,8 +1158,7 @@ void groth16_prove(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_o
   ZKP_REQUIRE(pk->shard_world == 0, ZKP_ERR_BAD_ARG);     // a sharded key yields partial sums only
   ctx->cur = &ctx->lanes[0];
   ctx->cur_idx = 0;
-  static const bool timeline = getenv("ZKP_TIMELINE") && atoi(getenv("ZKP_TIMELINE")) != 0;
-  ctx->tl_on = timeline && !ctx->profiling;
+  ctx->tl_on = ctx->tune.timeline && !ctx->profiling;
   if (pk->curve == ZKP_BN254) prove_enqueue<Bn254Fr>(ctx, pk, z, z_on_device, r, s, true);
   else prove_enqueue<Bls381Fr>(ctx, pk, z, z_on_device, r, s, true);
   ctx->tl_on = false;
@@ -1330,7 +1316,7 @@ struct RcclApi {
   std::string why;
 
   static void bring_up(std::shared_ptr<Attempt> at, std::vector<int> ids, int timeout_ms) {
-    const char* hang = getenv("ZKP_DEBUG_RCCL_HANG");
+    const char* hang = env_str("ZKP_DEBUG_RCCL_HANG");     // read live: this helper thread has no context
     Fns f;
     std::vector<void*> comms(ids.size(), nullptr);
     std::string why;

@@ -541,7 +541,7 @@ void marlin_prove(zkp_ctx* ctx, zkp_marlin_index* ix, uint64_t powers_g, uint64_
   // of the second round) starts its commitment MSM at once on an MSM workspace stream of this lane, under the NTTs / pointwise
   // kernels that compute the rest of the round (which otherwise run alone: 12.6 + 4.9 ms per proof in a kernel trace);
   // commit_round collects the result instead of launching the MSM.  ZKP_MARLIN_EARLY=0: every MSM inside commit_round.
-  static const bool early_on = !(getenv("ZKP_MARLIN_EARLY") && atoi(getenv("ZKP_MARLIN_EARLY")) == 0);
+  const bool early_on = ctx->tune.marlin_early;
   constexpr int EARLY_MAX = 16;
   if (!ix->early_pinned) ZKP_HIP(hipHostMalloc(reinterpret_cast<void**>(&ix->early_pinned), EARLY_MAX * 24 * 8));
   struct Early {
@@ -640,7 +640,7 @@ void marlin_prove(zkp_ctx* ctx, zkp_marlin_index* ix, uint64_t powers_g, uint64_
   // transforms with no MSM to overlap).  MEASURED NEUTRAL (profiles/r05_marlin_ab.txt: rounds 1 + 2 incl.
   // commits 16.1 ms without, 16.5 with: the first round's early MSMs simply take the vector ALUs the transforms left, the device is
   // saturated either way), so it is OFF by default; ZKP_MARLIN_EARLY_FFT=1 enables it; same proof bytes.
-  static const bool early_fft = getenv("ZKP_MARLIN_EARLY_FFT") && atoi(getenv("ZKP_MARLIN_EARLY_FFT")) != 0;
+  const bool early_fft = ctx->tune.marlin_early_fft;
   DVec z_poly = be.axpy(be.sub(be.shift(w_poly, xs), w_poly), x_poly, F.one_());      // w * v_X + x  (prover.rs:277-281)
   const size_t r2_size = next_pow2(std::max({mask.n, hs + (z_a.n + z_b.n - 1), hs + z_poly.n}));   // r_alpha and t have |H| coefficients
   DVec ZA_early, ZB_early, ZZ_early;
@@ -713,8 +713,7 @@ void marlin_prove(zkp_ctx* ctx, zkp_marlin_index* ix, uint64_t powers_g, uint64_
           has[k] = 1;
           collect_early(bearly[k], bj.data() + k * jw64);
         }
-      static const bool host_tail = !(getenv("ZKP_MARLIN_HOST_AFFINE") && atoi(getenv("ZKP_MARLIN_HOST_AFFINE")) == 0);
-      if (host_tail) {
+      if (ctx->tune.marlin_host_affine) {
         std::vector<HostJac> pts(slot.size());
         for (size_t k = 0; k < slot.size(); k++) {
           pts[k] = host_jac_load(chal.Fq, jac.data() + k * jw64);
@@ -833,7 +832,7 @@ void marlin_prove(zkp_ctx* ctx, zkp_marlin_index* ix, uint64_t powers_g, uint64_
   // Round 5: h_2's commitment starts before the round's host synchronisation, and the seven evaluations at beta (first- and
   // second-round polynomials: all known since the second round) run under its bucket sort instead of after gamma is known
   // — MEASURED SLOWER (profiles/r05_marlin_ab.txt: evaluations 1.0 -> 0.8 ms, batch_open +0.7 ms): OFF by default, ZKP_MARLIN_EARLY_EVAL=1 enables
-  static const bool early_eval = getenv("ZKP_MARLIN_EARLY_EVAL") && atoi(getenv("ZKP_MARLIN_EARLY_EVAL")) != 0;
+  const bool early_eval = ctx->tune.marlin_early_eval;
   uint64_t beta_evals[4 * G2_];
   if (early_eval) {
     commit_early(H2_);

@@ -97,7 +97,7 @@ struct BasesEntry {
   }
 };
 
-static int pick_window_bits(const zkp_cfg& cfg, size_t n, int group, bool lone) {
+static int pick_window_bits(const zkp_cfg& cfg, const zkp_tune& tune, size_t n, int group, bool lone) {
   if (group == 2 && cfg.msm_c_g2 >= 2 && cfg.msm_c_g2 <= 22) return cfg.msm_c_g2;       // zkp_ctx_config.msm_window_bits_g2 / ZKP_MSM_C_G2
   if (cfg.msm_c >= 2 && cfg.msm_c <= 22) return cfg.msm_c;                                // zkp_ctx_config.msm_window_bits / ZKP_MSM_C
   int lg = 0;
@@ -110,8 +110,7 @@ static int pick_window_bits(const zkp_cfg& cfg, size_t n, int group, bool lone) 
   // 0.951 -> 0.609 at 2^14), lg + 2 up to 2^17 (0.82 -> 0.705 at 2^16), lg + 1 at 2^18 / 2^19 (1.038 -> 0.957 at 2^18), lg from 2^20
   // on (c = 20 stays the optimum there and above: 19 and 21 both lose).  The queries of a Groth16 key keep round(log2 n): the
   // pipelined prover is VALU-bound, where twice the buckets is twice the reduction work (2^18 circuit: 495 -> 433 proofs/s widened).
-  static const bool widen = !(getenv("ZKP_MSM_WIDEN") && atoi(getenv("ZKP_MSM_WIDEN")) == 0);      // A/B: 0 = round(log2 n) everywhere
-  if (lone && widen && lg >= 10) lg += lg <= 14 ? 3 : lg <= 17 ? 2 : lg <= 19 ? 1 : 0;
+  if (lone && tune.msm_widen && lg >= 10) lg += lg <= 14 ? 3 : lg <= 17 ? 2 : lg <= 19 ? 1 : 0;   // A/B: ZKP_MSM_WIDEN=0 = round(log2 n) everywhere
   return std::min(20, std::max(4, lg));
 }
 
@@ -119,9 +118,9 @@ static int pick_window_bits(const zkp_cfg& cfg, size_t n, int group, bool lone) 
 struct WindowPlan {
   int c, W, wide, lgk, J;
 };
-static WindowPlan window_plan(const zkp_cfg& cfg, int scalar_bits, size_t n, int group, int c_hint, int lgk) {
-  static const bool balanced = !(getenv("ZKP_MSM_BALANCED") && atoi(getenv("ZKP_MSM_BALANCED")) == 0);
-  const int T = scalar_bits + 1, c0 = c_hint >= 2 && c_hint <= 22 ? c_hint : pick_window_bits(cfg, n, group, /*lone=*/c_hint == -1);
+static WindowPlan window_plan(const zkp_cfg& cfg, const zkp_tune& tune, int scalar_bits, size_t n, int group, int c_hint, int lgk) {
+  const bool balanced = tune.msm_balanced;
+  const int T = scalar_bits + 1, c0 = c_hint >= 2 && c_hint <= 22 ? c_hint : pick_window_bits(cfg, tune, n, group, /*lone=*/c_hint == -1);
   WindowPlan p{};
   if (lgk <= 0) {
     // Balanced windows: T = scalar_bits + 1 (one spare bit absorbs the last signed-digit carry) is spread over W = ceil(T / c)
@@ -150,7 +149,7 @@ static WindowPlan window_plan(const zkp_cfg& cfg, int scalar_bits, size_t n, int
 }
 size_t bases_table_bytes(zkp_ctx* ctx, int curve, int group, size_t n, int lgk) {
   const MsmVtbl* vt = msm_vtbl(curve, group);
-  return std::max<size_t>(1, n) * (size_t)window_plan(ctx->cfg, vt->scalar_bits, n, group, 0, lgk).J * vt->aff_bytes;
+  return std::max<size_t>(1, n) * (size_t)window_plan(ctx->cfg, ctx->tune, vt->scalar_bits, n, group, 0, lgk).J * vt->aff_bytes;
 }
 // Budget for resident window tables: ZKP_TABLE_BUDGET_GB (whole context) if set, else the free device memory minus a quarter of
 // the device for MSM / NTT scratch; what the context already holds is subtracted.
@@ -165,10 +164,10 @@ static double table_budget_left(zkp_ctx* ctx) {
   return left;
 }
 int bases_plan_lgk(zkp_ctx* ctx, int curve, const int* groups, const size_t* ns, int count) {
-  if (const char* e = getenv("ZKP_TABLE_K")) {                   // forced group size (tests)
-    int k = atoi(e), lg = 0;
+  if (const int k = ctx->tune.table_k) {                         // ZKP_TABLE_K: forced group size (tests), a power of two <= 2^6
+    int lg = 0;
     while ((1 << lg) < k) lg++;
-    return std::min(lg, 6);
+    return lg;
   }
   const double left = table_budget_left(ctx);
   for (int lgk = 0; lgk <= 6; lgk++) {
@@ -192,18 +191,15 @@ uint64_t bases_upload(zkp_ctx* ctx, int curve, int group, const uint64_t* xy, co
   // reduction tail of (c k - 1) doublings.
   int lgk = lgk_hint;
   if (lgk < 0) lgk = c_hint > 0 ? 0 : bases_plan_lgk(ctx, curve, &group, &n, 1);
-  const WindowPlan wp = window_plan(ctx->cfg, e->vt->scalar_bits, n, group, c_hint, lgk);
+  const WindowPlan wp = window_plan(ctx->cfg, ctx->tune, e->vt->scalar_bits, n, group, c_hint, lgk);
   e->c = wp.c;
   e->W = wp.W;
   e->wide = wp.wide;
   e->lgk = wp.lgk;
   e->var = wp.lgk > 0;
-  {
-    const char* env = group == 2 ? getenv("ZKP_TASK_CAP_G2") : nullptr;
-    if (!env) env = getenv("ZKP_TASK_CAP");
-    if (cap_hint >= 4) e->cap = std::min<uint32_t>(MSM_TASK_CAP, (uint32_t)cap_hint);
-    if (env && atoi(env) >= 4) e->cap = std::min<uint32_t>(MSM_TASK_CAP, (uint32_t)atoi(env));
-  }
+  static_assert(TUNE_TASK_CAP_MAX == (int)MSM_TASK_CAP && TUNE_PAIR_TOP_MAX == (int)PAIR_TOP_MAX, "tune.hpp restates both");
+  if (cap_hint >= 4) e->cap = std::min<uint32_t>(MSM_TASK_CAP, (uint32_t)cap_hint);
+  if (const int cap = group == 2 ? ctx->tune.task_cap_g2 : ctx->tune.task_cap) e->cap = (uint32_t)cap;   // ZKP_TASK_CAP(_G2): 4 .. MSM_TASK_CAP
   ZKP_REQUIRE((double)n * e->W < 2147483000.0, ZKP_ERR_BAD_ARG);
   const size_t ab = e->vt->aff_bytes;
   size_t bytes = std::max<size_t>(1, n) * wp.J * ab;
@@ -223,7 +219,7 @@ uint64_t bases_upload(zkp_ctx* ctx, int curve, int group, const uint64_t* xy, co
     ZKP_HIP(hipGetLastError());
     ZKP_HIP(hipStreamSynchronize(ctx->cur->stream));
   }
-  if (getenv("ZKP_DEBUG_MSM"))
+  if (env_str("ZKP_DEBUG_MSM"))                                  // read live: set on a context that already exists
     fprintf(stderr, "[msm] bases group=%d n=%zu: c=%d W=%d wide=%d k=%d copies=%d (%.2f GiB)\n", group, n, e->c, e->W, e->wide,
             1 << e->lgk, wp.J, (double)bytes / 1073741824.0);
   uint64_t h = ctx->next_handle++;
@@ -264,6 +260,8 @@ void msm_free_all(zkp_ctx* ctx) {
   ctx->table_bytes = 0;
   ctx->var_plans.clear();
 }
+// The shared entry keeps the plan of the context that BUILT it (window bits, window groups, task cap: what its tables and
+// src->tune at upload decided); dst->tune governs only how dst sorts and reduces an MSM over it.
 uint64_t bases_share(zkp_ctx* dst, zkp_ctx* src, uint64_t handle) {
   auto e = get_bases(src, handle);
   ZKP_REQUIRE(dst->device == src->device, ZKP_ERR_BAD_ARG);
@@ -833,7 +831,7 @@ void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scala
   // opening witnesses) shows 1-2 ms of sort kernels with the vector ALUs idle before its first accumulate launch (kernel trace,
   // profiles/r05_marlin_trace.txt) — so chunk 0 is per / ZKP_MSM_CHUNK_FIRST points (default 2: 57.7 -> 56.8 ms per Marlin proof, profiles/r05_marlin_ab.txt; 1 = equal chunks)
   // and the rest is split evenly.
-  static const size_t first_div = [] { const char* e = getenv("ZKP_MSM_CHUNK_FIRST"); long v = e ? atol(e) : 2; return (size_t)(v < 1 ? 1 : v); }();
+  const size_t first_div = (size_t)ctx->tune.msm_chunk_first;       // >= 1
   const size_t first = first_div > 1 ? std::max<size_t>(((per / first_div) + 255) & ~(size_t)255, 1024) : 0;
   const size_t rest = first && first < n ? n - first : n;
   const size_t nrest = (rest + per - 1) / per, per_rest = ((rest + nrest - 1) / nrest + 255) & ~(size_t)255;
@@ -948,7 +946,8 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     // K6: group entries by bucket (two-level counting sort); sorted values land back in `vals`
     // level-1 bins: enough of them that a bin (E / bins entries on average) fits the level-2 kernel's LDS stage; tiles:
     // 2048 scalars, more for large MSMs so that the (bin x tile) count matrix stays small
-    static const int h1_env = [] { const char* e = getenv("ZKP_SORT_H1"); return e ? atoi(e) : 0; }();
+    const zkp_tune& tune = ctx->tune;
+    const int h1_env = tune.sort_h1;
     int H1 = 10;
     while (H1 < SORT_H1_MAX && (E >> H1) > SORT_BIN_TARGET) H1++;
     if (h1_env > 0) H1 = std::min(SORT_H1_MAX, h1_env);
@@ -976,10 +975,9 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     const uint8_t* grp = scan_inf == be->sort_inf ? be->group_flags : nullptr;   // group bits only with the group's scan flags
     // staged level-1 scatter (sort_scatter_staged_kernel): sub-rounds of `staged_sub` scalars whose entries fit the LDS stage;
     // not for > 2048 level-1 bins (the two counter arrays would leave one workgroup per CU) or very narrow windows
-    static const bool staged_on = !(getenv("ZKP_SORT_STAGED") && atoi(getenv("ZKP_SORT_STAGED")) == 0);
     uint32_t staged_sub = 0;
     size_t staged_lds = 0;
-    if (staged_on && nbins1 <= 2048 && (size_t)256 * W * 8 <= SORT_STAGE_BYTES) {
+    if (tune.sort_staged && nbins1 <= 2048 && (size_t)256 * W * 8 <= SORT_STAGE_BYTES) {
       staged_sub = (uint32_t)(SORT_STAGE_BYTES / ((size_t)W * 8)) / 256 * 256;
       staged_sub = std::min<uint32_t>(staged_sub, tile);
       staged_lds = ((size_t)nbins1 + ((nbins1 + 3) & ~3u)) * 4 + (size_t)staged_sub * W * 8;
@@ -989,8 +987,7 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     if (reuse || l1_reuse) {
     } else {
       // threads per workgroup of the two level-1 passes (A/B: ZKP_SORT_NT_HIST / ZKP_SORT_NT_SCATTER = 256 restores rounds 3-5)
-      static const int nt_hist = [] { const char* e = getenv("ZKP_SORT_NT_HIST"); return e ? atoi(e) : 1024; }();
-      static const int nt_scat = [] { const char* e = getenv("ZKP_SORT_NT_SCATTER"); return e ? atoi(e) : 512; }();
+      const int nt_hist = tune.sort_nt_hist, nt_scat = tune.sort_nt_scatter;       // each 1024, 512 or 256
       auto level1 = [&](auto tag) {
         using FrP = decltype(tag);
         auto hist_l = [&](auto nt) {
@@ -1046,7 +1043,7 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
       hipLaunchKernelGGL(task_count_kernel, dim3((nb + 256) / 256), dim3(256), 0, st, start, end, nb, tcount, be->cap);
       exclusive_scan_u32(st, tcount, toff, (size_t)nb + 1, ws.scan_tmp2);
       // (1024 threads per workgroup since round 6: a quarter of the per-(block, length) global atomics on the 129 length counters)
-      static const uint32_t tnt = [] { const char* e = getenv("ZKP_TASK_NT"); const int v = e ? atoi(e) : 1024; return (uint32_t)(v >= 1024 ? 1024 : v >= 512 ? 512 : 256); }();
+      const uint32_t tnt = (uint32_t)tune.task_nt;                    // ZKP_TASK_NT: 1024, 512 or 256
       hipLaunchKernelGGL(task_fill_kernel, dim3((nb + tnt - 1) / tnt), dim3(tnt), 0, st, start, end, toff, nb, task_start,
                          task_len, task_dst, long_list, tmeta, be->cap);
       hipLaunchKernelGGL(task_cursor_kernel, dim3(1), dim3(64), 0, st, tmeta);
@@ -1062,7 +1059,7 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     MsmWorkspace& bws = bucket_ws >= 0 ? ctx->cur->ws[bucket_ws] : ws;
     char* buckets = reinterpret_cast<char*>(bws.buckets.get((size_t)2 * nb * XB + XB));
     char* task_partial = reinterpret_cast<char*>(ws.partial.get((size_t)max_tasks * XB));
-    static const bool zero_all = getenv("ZKP_MEMSET_BUCKETS") && atoi(getenv("ZKP_MEMSET_BUCKETS")) != 0;   // A/B: round-2 behaviour
+    const bool zero_all = tune.memset_buckets;                        // A/B: round-2 behaviour
     const uint32_t init = into >= 0 ? 1u : 0u;
     if (init) {
       ZKP_REQUIRE(bws.chain_nb == nb && bws.chain_xb == XB, ZKP_ERR_BAD_ARG);
@@ -1072,9 +1069,9 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     bws.chain_nb = 0;
     const bool timed = ms_accumulate && ctx->profiling;
     if (timed) ZKP_HIP(hipEventRecord(ctx->ev2, st));
-    static const uint32_t force_redo = getenv("ZKP_DEBUG_FORCE_REDO") && atoi(getenv("ZKP_DEBUG_FORCE_REDO")) != 0 ? 2u : 0u;   // tests
+    const uint32_t force_redo = tune.debug_force_redo ? 2u : 0u;      // tests
     ctx->mark(st, ":acc0");
-    vt->accumulate(st, be->table, sorted_vals, desc, toff + nb, max_tasks, buckets, task_partial,
+    vt->accumulate(st, tune, be->table, sorted_vals, desc, toff + nb, max_tasks, buckets, task_partial,
                    ws.redo.as<uint32_t>((size_t)max_tasks + 1), init | force_redo);
     ctx->mark(st, ":acc1");
     if (timed) {
@@ -1082,7 +1079,7 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
       ZKP_HIP(hipEventSynchronize(ctx->ev3));
       ZKP_HIP(hipEventElapsedTime(ms_accumulate, ctx->ev2, ctx->ev3));
     }
-    static const int dbg = [] { const char* e = getenv("ZKP_DEBUG_MSM"); return e ? atoi(e) : 0; }();
+    const int dbg = tune.debug_msm;
     if (dbg) {
       uint32_t* rep = ws.redo.as<uint32_t>((size_t)max_tasks + 1);     // accumulate is done with it
       ZKP_HIP(hipStreamSynchronize(st));
@@ -1160,21 +1157,15 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     // Round 6: the one-workgroup top of the pyramid and the segmented sums of the levels below it run in ONE launch (msm_group.hip
     // pair_top_segsum_kernel); the second stage then sums the partials of the low levels and, directly from the pyramid, the odd
     // entries of the top's levels (<= PAIR_TOP_MAX / 2 = one block each).  ZKP_PAIR_TOP_FUSE_SEG=0: pair_top, then both stages (rounds 3-5).
-    static const bool fuse_seg = !(getenv("ZKP_PAIR_TOP_FUSE_SEG") && atoi(getenv("ZKP_PAIR_TOP_FUSE_SEG")) == 0);
+    const bool fuse_seg = tune.pair_top_fuse_seg;
     int l_top = -1;                                // first level the fused top produces the successor of
     char* top_base = nullptr;
     uint32_t top_cnt = 0;
     for (int l = 0; l < L; l++) {
       uint32_t next_off = lvl_off + cnt;
-      static const bool top_fused = !(getenv("ZKP_PAIR_TOP") && atoi(getenv("ZKP_PAIR_TOP")) == 0);
-      // (rounded down to a power of two: the fused top starts at the level whose size EQUALS top_max)
-      static const uint32_t top_max = [] {
-        const char* e = getenv("ZKP_PAIR_TOP_MAX");
-        uint32_t v = e ? (uint32_t)atoi(e) : PAIR_TOP_MAX;
-        if (v < 2) v = PAIR_TOP_MAX;
-        while (v & (v - 1)) v &= v - 1;
-        return v;
-      }();
+      // (ZKP_PAIR_TOP_MAX is rounded down to a power of two: the fused top starts at the level whose size EQUALS top_max)
+      const bool top_fused = tune.pair_top;
+      const uint32_t top_max = (uint32_t)tune.pair_top_max;
       if (!top_fused || cnt > top_max) vt->pair(st, buckets + (size_t)lvl_off * XB, buckets + (size_t)next_off * XB, cnt / 2);
       else if (cnt == top_max || l == 0) {         // this level and all above it
         if (fuse_seg && cnt / 2 <= chunk) {
@@ -1325,10 +1316,7 @@ void msm_var_run(zkp_ctx* ctx, int curve, int group, const uint64_t* xy_host, co
   e.var = true;
   e.owns = false;
   e.c = n >= 4096 ? 16 : 8;
-  if (const char* env = getenv("ZKP_MSM_VAR_C")) {
-    int c = atoi(env);
-    if (c == 4 || c == 8 || c == 16) e.c = c;
-  }
+  if (ctx->tune.msm_var_c) e.c = ctx->tune.msm_var_c;                // ZKP_MSM_VAR_C: 4, 8 or 16
   e.W = 256 / e.c;
   e.wide = e.W;                // equal widths: the variable-base reduction weighs window w by 2^(c*w)
   while ((1 << e.lgk) < e.W) e.lgk++;          // one bucket set per window: the single "table copy" is the points themselves

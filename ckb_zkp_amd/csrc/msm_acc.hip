@@ -191,16 +191,15 @@ static uint32_t dbg_mask() {
   return 0x7fffffffu;
 #endif
 }
-void ZKP_CFG_SYM(msm_accumulate_launch)(hipStream_t s, const char* table, const uint32_t* vals, const uint4* desc,
+void ZKP_CFG_SYM(msm_accumulate_launch)(hipStream_t s, const zkp_tune& tune, const char* table, const uint32_t* vals, const uint4* desc,
                                         const uint32_t* n_tasks_dev, uint32_t max_tasks, char* buckets, char* partial,
                                         uint32_t* redo, uint32_t init) {
   // BLS12-381 G2: 1 wave/SIMD (VGPRs + AGPRs as spill space) vs 2 waves/SIMD (256 VGPRs + 168 B scratch since the round-3 streamed
   // reductions freed registers; it was 704 B in round 2, when two waves made the proof 8 % slower).  Round 4, 2^22 proofs on one box:
   // kernel 13.16 -> 12.29 ms, 0.717 -> 0.770 of the multiplier ceiling, 19.97 -> 20.15 proofs/s: two waves are the default
   // (ZKP_G2_ACC_OCC=1 restores).  BN254 G2 compiles to 213 VGPRs / two waves either way.
-  static const unsigned lds = [] { const char* e = getenv("ZKP_ACC_LDS_BYTES"); return e ? (unsigned)atoi(e) : 0u; }();
-  static const int occ = [] { const char* e = getenv("ZKP_G2_ACC_OCC"); return e ? atoi(e) : 2; }();
-  static const int occ1 = [] { const char* e = getenv("ZKP_G1_ACC_OCC"); return e ? atoi(e) : 3; }();
+  const unsigned lds = (unsigned)tune.acc_lds_bytes;
+  const int occ = tune.g2_acc_occ, occ1 = tune.g1_acc_occ;
   (void)hipMemsetAsync(redo, 0, sizeof(uint32_t), s);
   struct Redo {                                  // every launch path below is followed by the exact redo kernel
     hipStream_t s;
@@ -217,8 +216,7 @@ void ZKP_CFG_SYM(msm_accumulate_launch)(hipStream_t s, const char* table, const 
   } redo_after{s, table, vals, desc, buckets, partial, redo, init};
 #if ZKP_CFG_GROUP == 1 && defined(ZKP_ACC_UNSAT)
   // BLS12-381 G1: 169 VGPRs = one register over three waves per SIMD; ZKP_G1_ACC_WAVES=3 compiles for three (A/B switch)
-  static const int g1w = [] { const char* e = getenv("ZKP_G1_ACC_WAVES"); return e ? atoi(e) : 0; }();
-  if (g1w == 3)
+  if (tune.g1_acc_waves == 3)
     hipLaunchKernelGGL(accumulate_kernel<3>, dim3((max_tasks + 255) / 256), dim3(256), lds, s, table, vals, desc,
                        n_tasks_dev, buckets, partial, dbg_mask(), redo, init);
   else

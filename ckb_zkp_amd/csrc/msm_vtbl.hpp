@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "tune.hpp"
+
 namespace zkp {
 
 // Entries per block of the segmented sums (chunk / 256 - 1 serial additions per thread, then an 8-level LDS tree: the tree runs
@@ -41,7 +43,8 @@ struct MsmVtbl {
   // lane instead of four dependent random ones
   // init != 0: the bucket array already holds the buckets of another MSM (bucket chaining, ctx.hpp): a single-task bucket starts
   // from its stored value instead of the identity
-  void (*accumulate)(hipStream_t, const char* table, const uint32_t* vals, const uint4* desc,
+  // tune: the launcher's choices (LDS bytes, waves per SIMD the kernel was compiled for): it has no context of its own
+  void (*accumulate)(hipStream_t, const zkp_tune& tune, const char* table, const uint32_t* vals, const uint4* desc,
                      const uint32_t* n_tasks_dev, uint32_t max_tasks, char* buckets, char* partial, uint32_t* redo, uint32_t init);
   // redo: max_tasks + 1 words of scratch ([0] = count, zeroed by the launcher): tasks the fast path abandoned because an
   // operand might equal +-accumulator are listed there and redone by an exact second kernel

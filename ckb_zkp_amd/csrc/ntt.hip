@@ -34,15 +34,8 @@ constexpr int NTT_SMAX = 9;            // max radix bits per pass (default plan)
 // Round 5 (profiles/r05_ntt_two_pass.txt): a pass takes up to 9 radix bits on the same 1024-element tile (C = 1024 >> S columns per
 // row) — 2^22 .. 2^24 in three passes instead of four (-5 .. -8 % per transform), 2^18 in two; 2^20 / 2^21 keep 7+7+6 / 7+7+7.
 // ZKP_NTT_SMAX=7 restores the round-4 plans; 10 gives 2^20 in two passes (10 + 10, one column per row): measured +14 %, killed.
-// Read once per process (the cached inter-pass tables depend on the plan).
-static int ntt_smax() {
-  static const int v = [] {
-    const char* e = getenv("ZKP_NTT_SMAX");
-    int s = e ? atoi(e) : NTT_SMAX;
-    return s < 4 ? 4 : (s > 10 ? 10 : s);
-  }();
-  return v;
-}
+// ctx->tune.ntt_smax, latched per context like the cached inter-pass tables (ctx->ntt_tables) that depend on the plan.
+static_assert(zkp_tune{}.ntt_smax == NTT_SMAX, "tune.hpp: default of ZKP_NTT_SMAX");
 #ifndef ZKP_NTT_TILE_LOG
 #define ZKP_NTT_TILE_LOG 10
 #endif
@@ -589,30 +582,25 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_pass2_kernel(NttPassArgs a) {
     F::reduce_once(r).store(out + (size_t)oidx * 8);
   }
 }
-static bool ntt_v2() {
-  static const bool on = !(getenv("ZKP_NTT_V2") && atoi(getenv("ZKP_NTT_V2")) == 0);
-  return on;
-}
-// one pass: the kernel and the LDS size that goes with it
+// one pass: the kernel and the LDS size that goes with it (v2: ctx->tune.ntt_v2)
 template <class P>
-static void ntt_launch(hipStream_t st, const NttPassArgs& a, uint32_t grid, int count) {
+static void ntt_launch(hipStream_t st, bool v2, const NttPassArgs& a, uint32_t grid, int count) {
   const size_t tile = (size_t)1 << (a.S + a.logC);
   const size_t tw_bytes = ((size_t)1 << a.S) / 2 * 4 * Fu<P>::L + 32;
-  if (ntt_v2() && tile == ((size_t)1 << NTT_TILE_LOG))
+  if (v2 && tile == ((size_t)1 << NTT_TILE_LOG))
     hipLaunchKernelGGL((ntt_pass2_kernel<P, (1 << NTT_TILE_LOG)>), dim3(grid, count), dim3(NTT_THREADS),
                        NTT2_PLANE(tile) * 4 * Fu<P>::L + tw_bytes, st, a);
-  else if (ntt_v2())
+  else if (v2)
     hipLaunchKernelGGL((ntt_pass2_kernel<P, 0>), dim3(grid, count), dim3(NTT_THREADS), NTT2_PLANE(tile) * 4 * Fu<P>::L + tw_bytes, st, a);
   else
     hipLaunchKernelGGL(ntt_pass_kernel<P>, dim3(grid, count), dim3(NTT_THREADS), tile * 32 + tw_bytes, st, a);
 }
 
-static void ntt_plan(int log_n, int* S, int* P) {
+static void ntt_plan(int smax, int log_n, int* S, int* P) {
   if (log_n == 0) {
     *P = 0;
     return;
   }
-  const int smax = ntt_smax();
   int p = (log_n + smax - 1) / smax;
   int base = log_n / p, rem = log_n % p;
   for (int i = 0; i < p; i++) S[i] = base + (i < rem ? 1 : 0);
@@ -623,15 +611,14 @@ static void ntt_plan(int log_n, int* S, int* P) {
 template <class P>
 static uint32_t* full_table(zkp_ctx* ctx, NttTables& t, uint32_t** slot, const uint32_t* lo, const uint32_t* hi, int S,
                             int logB, int twiddle) {
-  static const bool enabled = !(getenv("ZKP_NTT_FULL") && atoi(getenv("ZKP_NTT_FULL")) == 0);   // A/B switch
-  if (!enabled || t.log_n > NTT_FULL_MAX_LOG || t.log_n < 2) return nullptr;
+  if (!ctx->tune.ntt_full || t.log_n > NTT_FULL_MAX_LOG || t.log_n < 2) return nullptr;
   if (*slot) return *slot;
   const size_t N = (size_t)1 << t.log_n;
   uint32_t* blk;
   if (hipMalloc(&blk, N * 32) != hipSuccess) return nullptr;        // fall back to the two-level lookup
   hipStream_t s = ctx->cur->stream;
   hipLaunchKernelGGL(ntt_full_table_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, s, blk, lo, hi, t.h, (uint32_t)N, S,
-                     logB, twiddle, ntt_v2() ? 1 : 0);
+                     logB, twiddle, ctx->tune.ntt_v2 ? 1 : 0);
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipStreamSynchronize(s));       // shared by every lane / stream afterwards
   t.extra.push_back(blk);
@@ -649,7 +636,7 @@ void ntt_run_t(zkp_ctx* ctx, int curve, uint32_t* const* data, int count, int lo
   NttTables& t = get_tables<P>(ctx, curve, log_n);
   const size_t N = (size_t)1 << log_n;
   int S[8], np;
-  ntt_plan(log_n, S, &np);
+  ntt_plan(ctx->tune.ntt_smax, log_n, S, &np);
   // buffers: an even pass count ping-pongs data <-> scratch and ends in `data`; an odd one would end in scratch and pay a copy
   // (13 us of a 164 us transform at 2^20: three passes) — with a second scratch region its passes go data -> s0 -> s1 -> ... ->
   // data instead (round 4)
@@ -701,7 +688,7 @@ void ntt_run_t(zkp_ctx* ctx, int curve, uint32_t* const* data, int count, int lo
         a.post_const = t.n_inv;
       }
     }
-    ntt_launch<P>(ctx->cur->stream, a, (uint32_t)(N >> (S[p] + logC)), count);
+    ntt_launch<P>(ctx->cur->stream, ctx->tune.ntt_v2, a, (uint32_t)(N >> (S[p] + logC)), count);
     src_base = dst_base;
     logB += S[p];
   }
@@ -729,7 +716,7 @@ static void launch_pass(zkp_ctx* ctx, NttTables& t, int log_n, const int* S, int
   a.tw_lo = inverse ? t.wi_lo : t.w_lo;
   a.tw_hi = inverse ? t.wi_hi : t.w_hi;
   if (!a.last) a.tw_full = full_table<P>(ctx, t, inverse ? &t.full_inv[p] : &t.full_fwd[p], a.tw_lo, a.tw_hi, S[p], logB, 1);
-  ntt_launch<P>(ctx->cur->stream, a, (uint32_t)(((size_t)1 << log_n) >> (S[p] + logC)), 1);
+  ntt_launch<P>(ctx->cur->stream, ctx->tune.ntt_v2, a, (uint32_t)(((size_t)1 << log_n) >> (S[p] + logC)), 1);
 }
 
 // Witness map, first half (r1cs_to_qap.rs:144-148,161-162): ifft_in_place followed by coset_fft_in_place of the same vector
@@ -744,7 +731,7 @@ static bool ntt_ifft_coset_fft_t(zkp_ctx* ctx, int curve, uint32_t* data, int lo
   const size_t N = (size_t)1 << log_n;
   uint32_t* scratch = ctx->cur->ntt_scratch.as<uint32_t>(N * 8);
   int S[8], np;
-  ntt_plan(log_n, S, &np);
+  ntt_plan(ctx->tune.ntt_smax, log_n, S, &np);
   uint32_t* buf[2] = {data, scratch};
   int cur = 0;
   for (int half = 0; half < 2; half++) {
@@ -773,7 +760,7 @@ static uint32_t* ntt_qap_coset_ifft_t(zkp_ctx* ctx, int curve, uint32_t* a_, uin
   const size_t N = (size_t)1 << log_n;
   uint32_t* scratch = ctx->cur->ntt_scratch.as<uint32_t>(N * 8);
   int S[8], np;
-  ntt_plan(log_n, S, &np);
+  ntt_plan(ctx->tune.ntt_smax, log_n, S, &np);
   if (np < 2) return nullptr;
   // pass 0: (a, b, c) -> scratch; then scratch <-> a; an odd pass count ends in b (free once pass 0 has read it)
   const uint32_t* in = a_;
@@ -802,15 +789,13 @@ static uint32_t* ntt_qap_coset_ifft_t(zkp_ctx* ctx, int curve, uint32_t* a_, uin
 }
 
 bool ntt_ifft_coset_fft(zkp_ctx* ctx, int curve, uint32_t* data, int log_n) {
-  static const bool on = !(getenv("ZKP_NTT_FUSE") && atoi(getenv("ZKP_NTT_FUSE")) == 0);
-  if (!on) return false;
+  if (!ctx->tune.ntt_fuse) return false;
   if (curve == ZKP_BN254) return ntt_ifft_coset_fft_t<Bn254Fr>(ctx, curve, data, log_n);
   if (curve == ZKP_BLS12_381) return ntt_ifft_coset_fft_t<Bls381Fr>(ctx, curve, data, log_n);
   throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};
 }
 uint32_t* ntt_qap_coset_ifft(zkp_ctx* ctx, int curve, uint32_t* a, uint32_t* b, uint32_t* c, const uint32_t* zinv, int log_n) {
-  static const bool on = !(getenv("ZKP_NTT_FUSE") && atoi(getenv("ZKP_NTT_FUSE")) == 0);
-  if (!on) return nullptr;
+  if (!ctx->tune.ntt_fuse) return nullptr;
   if (curve == ZKP_BN254) return ntt_qap_coset_ifft_t<Bn254Fr>(ctx, curve, a, b, c, zinv, log_n);
   if (curve == ZKP_BLS12_381) return ntt_qap_coset_ifft_t<Bls381Fr>(ctx, curve, a, b, c, zinv, log_n);
   throw StatusError{ZKP_ERR_UNSUPPORTED_CURVE};

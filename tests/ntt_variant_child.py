@@ -1,7 +1,8 @@
 """NTT variants, one fresh process per switch setting (tests/test_gpu_ntt_variants.py).
 
-The switches of csrc/ntt.hip (ZKP_NTT_V2 / _FULL / _FUSE / _SMAX) and ZKP_NTT_BATCH of the witness map are `static` and read once
-per process, so every setting is checked by a child of its own:
+The switches of csrc/ntt.hip (ZKP_NTT_V2 / _FULL / _FUSE / _SMAX) and ZKP_NTT_BATCH of the witness map are latched by a context when
+it is created (csrc/tune.hpp).  Every setting is still checked by a child of its own, so that a child that faults stops the
+run (last paragraph) instead of taking the other settings' checks with it:
 
     python -m tests.ntt_variant_child '{"ntt": [log_n, ...], "witness": [k, ...]}'      (switches in the environment)
 
@@ -59,7 +60,7 @@ VARIANTS = [
 
 # ------------------------------------------------------------------------------------------------ spec arithmetic (no GPU)
 def smax_of(env) -> int:
-    """ntt_smax() of csrc/ntt.hip: ZKP_NTT_SMAX clamped to 4..10, default 9"""
+    """ntt_smax of csrc/tune.hpp: ZKP_NTT_SMAX clamped to 4..10, default 9"""
     e = env.get("ZKP_NTT_SMAX")
     s = int(e) if e else DEFAULT_SMAX
     return min(max(s, 4), 10)

@@ -77,3 +77,38 @@ def test_config_validation_and_forward_compatible_struct_size(ctx):
     assert lib.zkp_ctx_destroy(h) == 0
     with pytest.raises(KeyError):
         _lib.make_config(dict(no_such_field=1))
+
+
+def test_two_contexts_latch_different_internal_switches(ctx, monkeypatch):
+    """The internal A/B switches (csrc/tune.hpp) are latched per CONTEXT when it is created, like the public fields above: context B is
+    created under ZKP_TABLE_K=2, ZKP_NTT_SMAX=4 and ZKP_SORT_STAGED=0, context A under a clean environment, and the variables are gone
+    again before either key is uploaded or anything is proved.  B's key reports window groups of 2 and A's groups of 1 (a switch read
+    at upload would give 1 on both, a process-wide latch the same on both), and both prove the byte-identical proof
+    (tests/test_gpu_groth16.py ties the proof of this circuit and size to the oracle)."""
+    switches = {"ZKP_TABLE_K": "2", "ZKP_NTT_SMAX": "4", "ZKP_SORT_STAGED": "0"}
+    for name in switches:
+        monkeypatch.delenv(name, raising=False)
+    inst = mimc_chain_instance("bn254", samples_for_domain(10))
+    params = groth16.generate_parameters(ctx, "bn254", inst, **TOXIC)
+    c = params.curve
+    z = codec.fr_to_mont(inst.z, c).reshape(-1, 4)
+    r, s = codec.fr_to_mont([0x1F2E3D4C5B6A7988, 0x8899AABBCCDDEEFF], c)
+    a = Context(ctx.device)
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    b = Context(ctx.device)
+    for name in switches:
+        monkeypatch.delenv(name)
+    pks = []
+    try:
+        pks = [groth16.ProvingKey(x, params, inst) for x in (a, b)]
+        assert [pk.domain_size for pk in pks] == [1 << 10] * 2
+        assert [pk.table_plan()["window_group"] for pk in pks] == [1, 2]
+        (out_a, inf_a), (out_b, inf_b) = [pk.prove_raw(z, r, s) for pk in pks]
+        assert out_a.any()
+        assert out_a.tobytes() == out_b.tobytes() and inf_a.tobytes() == inf_b.tobytes()
+    finally:
+        for pk in pks:
+            pk.free()
+        a.close()
+        b.close()

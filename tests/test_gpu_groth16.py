@@ -256,7 +256,7 @@ def test_full_size_proof_trapdoor_and_pipeline(ctx, curve, k):
 
 def test_graph_replay_equals_eager():
     """ZKP_GRAPH=1: the third and later proofs on a lane replay a captured hipGraph; they must equal the eager proofs
-    (own process: the switch is read once per process)."""
+    (own processes: a context latches the switch when it is created)."""
     code = r'''
 import numpy as np, random
 from ckb_zkp_amd import codec, groth16
@@ -281,7 +281,7 @@ print("PROOFS", outs.tobytes().hex(), infs.tobytes().hex())
     assert res["0"] == res["1"]
 
 
-def _proofs_in_subprocess(code, **env_extra):
+def _proofs_in_subprocess(code, all_lines=False, **env_extra):
     import os
     import subprocess
     import sys
@@ -289,7 +289,8 @@ def _proofs_in_subprocess(code, **env_extra):
     env = dict(os.environ, PYTHONPATH=root, **env_extra)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
-    return [l for l in out.stdout.splitlines() if l.startswith("PROOFS")][0]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("PROOFS")]
+    return lines if all_lines else lines[0]
 
 
 _SWITCH_CODE = r'''
@@ -315,15 +316,29 @@ assert np.array_equal(one, outs[0]) and np.array_equal(inf1, infs[0])
 print("PROOFS", outs.tobytes().hex(), infs.tobytes().hex())
 '''
 
+# one process for every switch set: the body above once per set, each under its own environment and in a context of its own
+_SWITCH_LOOP = r'''
+import os
+for sw in %r:
+    os.environ.update(sw)
+    scope = {}
+    exec(%r, scope)
+    scope["ctx"].dev_free(scope["zd"])
+    scope["pk"].free()
+    scope["ctx"].close()                       # destroyed before the next one is created
+    for name in sw:
+        del os.environ[name]
+'''
+
 
 def test_schedule_switches_do_not_change_the_proof():
     """Every scheduling shortcut of the prover — bucket chaining (H accumulates into L's buckets, one reduction for l' + h_acc),
     the shared level-1 pass, shared sorts, the staged scatter, the three-stream plan, window groups, the unsaturated NTT pass and its
     full-size tables / fused chains, the batched witness-map transforms and a three-pass NTT plan, the evaluation-form key
     (transformed H query, C folded into the L query), the host-side into_affine — is an optimisation only: proofs are
-    byte-identical with each one switched off (own processes: the switches are read once per process)."""
-    base = _proofs_in_subprocess(_SWITCH_CODE)
-    for sw in ({"ZKP_CHAIN_LH": "0"}, {"ZKP_SHARE_L1": "0"}, {"ZKP_SHARE_B_SORT": "0", "ZKP_SHARE_AL_SORT": "0"},
+    byte-identical with each one switched off.  A context latches its switches when it is created (csrc/tune.hpp), so ONE child process
+    runs every set: it updates its environment, creates a fresh Context, proves, prints one PROOFS line and destroys the context."""
+    sets = ({}, {"ZKP_CHAIN_LH": "0"}, {"ZKP_SHARE_L1": "0"}, {"ZKP_SHARE_B_SORT": "0", "ZKP_SHARE_AL_SORT": "0"},
                {"ZKP_SORT_STAGED": "0"}, {"ZKP_SINGLE_STREAM": "1"}, {"ZKP_LATENCY_PLAN": "0"}, {"ZKP_TABLE_K": "2"},
                {"ZKP_NTT_V2": "0"}, {"ZKP_NTT_FULL": "0"}, {"ZKP_NTT_FUSE": "0"},
                # a, b, c transformed by one launch each (grid.y = 3); 2^12 as 4 + 4 + 4, an odd pass count; both
@@ -331,8 +346,11 @@ def test_schedule_switches_do_not_change_the_proof():
                # the key in coefficient form (no transformed H query, C not folded into L), H alone transformed, host / device into_affine
                {"ZKP_H_LAGRANGE": "0"}, {"ZKP_C_FOLD": "0"}, {"ZKP_HOST_AFFINE": "0"},
                # every eighth accumulate task through the exact (redo) kernel: on top of chained buckets, and without chaining
-               {"ZKP_DEBUG_FORCE_REDO": "1"}, {"ZKP_DEBUG_FORCE_REDO": "1", "ZKP_CHAIN_LH": "0"}):
-        assert _proofs_in_subprocess(_SWITCH_CODE, **sw) == base, sw
+               {"ZKP_DEBUG_FORCE_REDO": "1"}, {"ZKP_DEBUG_FORCE_REDO": "1", "ZKP_CHAIN_LH": "0"})
+    lines = _proofs_in_subprocess(_SWITCH_LOOP % (sets, _SWITCH_CODE), all_lines=True)
+    assert len(lines) == len(sets)
+    for sw, line in zip(sets, lines):
+        assert line == lines[0], sw
 
 
 

@@ -58,8 +58,8 @@ def test_prove_multi_sharded_equals_single_gpu(ctx, curve, k, world):
 
 
 def test_prove_multi_replicated_witness_map(ctx, monkeypatch):
-    """ZKP_MULTI_WM_SPLIT=0 is read once per process, so the replicated-witness-map variant of the 3-rank step runs in a
-    child process and must print the same proof as the task-split one."""
+    """ZKP_MULTI_WM_SPLIT=0 is read when a context is created (zkp_cfg): the replicated-witness-map variant of the 3-rank step runs
+    in a child process of its own and must print the same proof as the task-split one."""
     code = r'''
 import numpy as np
 from ckb_zkp_amd import codec, groth16
