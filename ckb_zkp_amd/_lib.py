@@ -155,6 +155,12 @@ SIGNATURES = {
     "zkp_fr_eq_evals_dev": (C.c_int32, [vp, C.c_int, vp, C.c_size_t, vp]),
     "zkp_fr_product_circuit_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_fr_memcheck_circuits_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]),
+    "zkp_gkr_layer_upload": (C.c_int32, [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.POINTER(vp)]),
+    "zkp_gkr_layer_free": (C.c_int32, [vp, vp]),
+    "zkp_gkr_layer_info": (C.c_int32, [vp, u64p]),
+    "zkp_fr_gkr_eval_layer_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp]),
+    "zkp_fr_gkr_tables_dev": (C.c_int32, [vp, C.c_int, vp, C.c_int32, vp, vp, vp]),
+    "zkp_fr_gkr_round_dev": (C.c_int32, [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, vp]),
     "zkp_msm_g1_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g2_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g1_mont_batch_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, vp, vp, vp]),

@@ -301,6 +301,52 @@ class Context:
                    "zkp_fr_memcheck_circuits_dev")
         return roots
 
+    def gkr_layer_upload(self, op, left, right, log_in: int) -> int:
+        """zkp_gkr_layer_upload: the wiring of one layer (op 0 = add / 1 = mul, left / right < 2^log_in) -> handle"""
+        op = np.ascontiguousarray(op, dtype=np.uint8)
+        left, right = np.ascontiguousarray(left, dtype=np.uint32), np.ascontiguousarray(right, dtype=np.uint32)
+        assert len(op) == len(left) == len(right)
+        h = C.c_void_p()
+        _lib.check(self.lib.zkp_gkr_layer_upload(self.h, _ptr(op), _ptr(left), _ptr(right), len(op), log_in, C.byref(h)),
+                   "zkp_gkr_layer_upload")
+        return h.value
+
+    def gkr_layer_free(self, layer: int):
+        _lib.check(self.lib.zkp_gkr_layer_free(self.h, C.c_void_p(layer)), "zkp_gkr_layer_free")
+
+    def gkr_layer_info(self, layer: int) -> dict:
+        """zkp_gkr_layer_info: n_gates, log_out, log_in, n_mul, max_fan_left, max_fan_right, long_left, long_right"""
+        info = (C.c_uint64 * 8)()
+        _lib.check(self.lib.zkp_gkr_layer_info(C.c_void_p(layer), info), "zkp_gkr_layer_info")
+        return dict(zip(("n_gates", "log_out", "log_in", "n_mul", "max_fan_left", "max_fan_right", "long_left", "long_right"),
+                        (int(v) for v in info)))
+
+    def fr_gkr_eval_layer_dev(self, curve, layer: int, in_ptr: int, out_ptr: int):
+        """zkp_fr_gkr_eval_layer_dev: out[g] = in[left] (+ or *) in[right], zeros up to 2^log_out; DEVICE Montgomery Fr"""
+        _lib.check(self.lib.zkp_fr_gkr_eval_layer_dev(self.h, get_curve(curve).cid, C.c_void_p(layer), C.c_void_p(in_ptr or 0),
+                                                      C.c_void_p(out_ptr or 0)), "zkp_fr_gkr_eval_layer_dev")
+
+    def fr_gkr_tables_dev(self, curve, layer: int, phase: int, g_ptr: int, w_ptr: int, outs):
+        """zkp_fr_gkr_tables_dev: phase 1 (eval_hg): outs = mul, add1, add2 by left node, w = V; phase 2 (eval_fgu): outs = mul, add
+        by right node, w = eq(ru).  Everything DEVICE Montgomery Fr: g 2^log_out, w and each output 2^log_in."""
+        outs = list(outs) + [None] * (3 - len(outs))
+        oa = (C.c_void_p * 3)(*[p or None for p in outs])
+        _lib.check(self.lib.zkp_fr_gkr_tables_dev(self.h, get_curve(curve).cid, C.c_void_p(layer), phase, C.c_void_p(g_ptr or 0),
+                                                  C.c_void_p(w_ptr or 0), oa), "zkp_fr_gkr_tables_dev")
+
+    def fr_gkr_round_dev(self, curve, phase: int, tables, length: int, fu=None, bind=None, want_evals: bool = True):
+        """zkp_fr_gkr_round_dev over DEVICE tables of `length` Fr (phase 1: f, mul, add1, add2; phase 2: f, mul, add and the
+        Montgomery constant fu).  bind: one Montgomery Fr bound into every table first (length halves), or None.
+        Returns the (2, 4) uint64 Montgomery g(0), g(2), or None without want_evals."""
+        assert len(tables) == (4 if phase == 1 else 3)
+        ta = (C.c_void_p * len(tables))(*[p or None for p in tables])
+        x = None if bind is None else _c64(bind)
+        f = None if fu is None else _c64(fu)
+        out = np.zeros((2, 4), dtype=np.uint64) if want_evals else None
+        _lib.check(self.lib.zkp_fr_gkr_round_dev(self.h, get_curve(curve).cid, phase, ta, length, _ptr(f), _ptr(x), _ptr(out)),
+                   "zkp_fr_gkr_round_dev")
+        return out
+
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)
         xyz = _c64(xyz)

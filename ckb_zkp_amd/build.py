@@ -40,7 +40,8 @@ UNITS = [("ntt.hip", "ntt.o", ["-DZKP_INLINE_MUL"]),
          ("fs_rng.cpp", "fs_rng.o", []),
          ("marlin.hip", "marlin.o", []),
          ("sumcheck.hip", "sumcheck.o", ["-DZKP_INLINE_MUL"]),     # fused sum-check round + eq table, Fr only: both curves in one object
-         ("spark.hip", "spark.o", ["-DZKP_INLINE_MUL"])]           # SPARK memory-checking hashes + product circuits, Fr only likewise
+         ("spark.hip", "spark.o", ["-DZKP_INLINE_MUL"]),           # SPARK memory-checking hashes + product circuits, Fr only likewise
+         ("gkr.hip", "gkr.o", ["-DZKP_INLINE_MUL"])]               # Libra GKR layer evaluation, bookkeeping tables + fused rounds, Fr only likewise
 for _c, _g in CONFIGS:
     _d = [f"-DZKP_CFG_CURVE={_c}", f"-DZKP_CFG_GROUP={_g}"]
     UNITS.append(("msm_group.hip", f"msm_group_c{_c}{_g}.o", _d + (["-DZKP_INLINE_MUL"] if (_c, _g) in ((0, 1), (0, 2), (1, 1)) else [])))

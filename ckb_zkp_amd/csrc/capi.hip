@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "ctx.hpp"
+#include "gkr.hpp"
 #include "host_field.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
@@ -483,6 +484,34 @@ int32_t zkp_fr_memcheck_circuits_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t cou
   return guarded(ctx, [&] {
     fr_spark_circuits(ctx, curve, count, addr_dev, val_dev, ts_dev, ts_add, circuits_dev, n, gamma1_host, gamma2_host, roots_host);
   });
+}
+int32_t zkp_gkr_layer_upload(zkp_ctx* ctx, const uint8_t* op_host, const uint32_t* left_host, const uint32_t* right_host, size_t n_gates,
+                             uint32_t log_in, zkp_gkr_layer** layer) {
+  if (!op_host || !left_host || !right_host || !layer) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { *layer = gkr_layer_upload(ctx, op_host, left_host, right_host, n_gates, log_in); });
+}
+int32_t zkp_gkr_layer_free(zkp_ctx* ctx, zkp_gkr_layer* layer) {
+  if (!layer) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { gkr_layer_free(ctx, layer); });
+}
+int32_t zkp_gkr_layer_info(const zkp_gkr_layer* layer, uint64_t info[8]) {
+  if (!layer || !info) return ZKP_ERR_BAD_ARG;
+  gkr_layer_info(layer, info);
+  return ZKP_OK;
+}
+int32_t zkp_fr_gkr_eval_layer_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, const uint64_t* in_dev, uint64_t* out_dev) {
+  if (!layer || !in_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_gkr_eval_layer(ctx, curve, layer, in_dev, out_dev); });
+}
+int32_t zkp_fr_gkr_tables_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, int32_t phase, const uint64_t* g_dev,
+                              const uint64_t* w_dev, uint64_t* const* out_dev) {
+  if (!layer || !g_dev || !w_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_gkr_tables(ctx, curve, layer, phase, g_dev, w_dev, out_dev); });
+}
+int32_t zkp_fr_gkr_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t phase, uint64_t* const* tables_dev, size_t len,
+                             const uint64_t* fu_host, const uint64_t* bind_host, uint64_t* evals_out_host) {
+  if (!tables_dev || (!bind_host && !evals_out_host)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_gkr_round(ctx, curve, phase, tables_dev, len, fu_host, bind_host, evals_out_host); });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

@@ -19,7 +19,8 @@ from .codec import fr_int, fr_mont
 from .params import get_curve
 
 
-def _first(ctx, ptr: int, c) -> int:
+def first_element(ctx, ptr: int, c) -> int:
+    """element 0 of a DEVICE table as an integer: where a bound table leaves its final value"""
     a = np.zeros(4, dtype=np.uint64)
     ctx.d2h(a, ptr)
     return fr_int(a, c)
@@ -40,7 +41,8 @@ def quadratic_coeffs(e0: int, e2: int, claim: int, r: int) -> list:
     return [e0 % r, (e1 - a - e0) % r, a]
 
 
-def _evaluate(coeffs, x: int, r: int) -> int:
+def evaluate_poly(coeffs, x: int, r: int) -> int:
+    """a round polynomial (constant term first) at x"""
     acc = 0
     for cf in reversed(coeffs):
         acc = (acc * x + cf) % r
@@ -60,7 +62,7 @@ def _prove(ctx, c, kind, tables, n, claim, next_challenge, to_coeffs):
             length //= 2
         coeffs = to_coeffs([tuple(fr_int(p, c) for p in term) for term in ev], claim)
         x = next_challenge(list(coeffs)) % r
-        claim = _evaluate(coeffs, x, r)
+        claim = evaluate_poly(coeffs, x, r)
         polys.append(coeffs)
         rs.append(x)
     if x is not None:
@@ -73,14 +75,14 @@ def prove_phase_one(ctx, curve, d_eq, d_a, d_b, d_c, n, claim, next_challenge):
     c = get_curve(curve)
     polys, rx = _prove(ctx, c, SC_EQ_AB_MINUS_C, [d_eq, d_a, d_b, d_c], n, claim, next_challenge,
                        lambda ev, cl: cubic_coeffs(*ev[0], cl, c.r))
-    return polys, rx, tuple(_first(ctx, p, c) for p in (d_a, d_b, d_c, d_eq))
+    return polys, rx, tuple(first_element(ctx, p, c) for p in (d_a, d_b, d_c, d_eq))
 
 
 def prove_phase_two(ctx, curve, d_abc, d_z, n, claim, next_challenge):
     """sum_check_proof_phase_two: g = abc z over DEVICE tables of n Fr.  Returns (polys, ry, (vs, vz))."""
     c = get_curve(curve)
     polys, ry = _prove(ctx, c, SC_PROD2, [d_abc, d_z], n, claim, next_challenge, lambda ev, cl: quadratic_coeffs(*ev[0], cl, c.r))
-    return polys, ry, tuple(_first(ctx, p, c) for p in (d_abc, d_z))
+    return polys, ry, tuple(first_element(ctx, p, c) for p in (d_abc, d_z))
 
 
 def prove_cubic_batched(ctx, curve, par, c_par, seq, coeffs, n, claim, next_challenge):
@@ -97,7 +99,7 @@ def prove_cubic_batched(ctx, curve, par, c_par, seq, coeffs, n, claim, next_chal
         return cubic_coeffs(s[0], s[1], s[2], cl, r)
 
     polys, rs = _prove(ctx, c, SC_PROD3, tables, n, claim, next_challenge, to_coeffs)
-    f = lambda p: _first(ctx, p, c)                                # noqa: E731
+    f = lambda p: first_element(ctx, p, c)                                # noqa: E731
     return (polys, rs, ([f(a) for a, _ in par], [f(b) for _, b in par], f(c_par) if par else None),
             ([f(a) for a, _, _ in seq], [f(b) for _, b, _ in seq], [f(t) for _, _, t in seq]))
 

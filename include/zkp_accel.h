@@ -50,7 +50,8 @@ typedef struct zkp_ctx zkp_ctx; /* opaque: device, stream, twiddle tables, scrat
 const char* zkp_status_string(int32_t status);
 /* "zkp_accel <major.minor> (gfx950)".  0.7.1: zkp_g1_ipa_fold_dev (IPA generator fold) / zkp_fr_dot_batch_dev (batched Fr inner
  * products); later in 0.7.1, detected by symbol: zkp_fr_sumcheck_round_dev (fused sum-check round) / zkp_fr_eq_evals_dev (eq
- * table), then zkp_fr_product_circuit_dev / zkp_fr_memcheck_circuits_dev (SPARK memory-checking hashes and product circuits).
+ * table), then zkp_fr_product_circuit_dev / zkp_fr_memcheck_circuits_dev (SPARK memory-checking hashes and product circuits),
+ * then zkp_gkr_layer_upload / _free / _info and zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev (Libra GKR).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -287,6 +288,57 @@ int32_t zkp_fr_memcheck_circuits_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t cou
                                      const uint64_t* const* val_dev, const uint32_t* const* ts_dev, const uint32_t* ts_add,
                                      uint64_t* const* circuits_dev, size_t n, const uint64_t* gamma1_host,
                                      const uint64_t* gamma2_host, uint64_t* roots_host);
+/* Libra's linear-time GKR (later in 0.7.1, detected by symbol): the table work of one circuit layer in the loop of
+ * LinearGKRProof::prover (libra/src/libra_linear_gkr.rs:22-114) and of its ZK twin (libra_zk_linear_gkr.rs), every table kept on
+ * the device.  Commitments, blinds and the transcript stay with the caller.
+ *
+ * The wiring of one layer, Layer::mid_layer_new (libra/src/circuit.rs:55-80): gate g = (op[g], left[g], right[g]), op 0 = add,
+ * 1 = mul, left / right < 2^log_in the nodes of the layer below.  op_host / left_host / right_host: n_gates values each, host
+ * memory.  1 <= n_gates <= 2^28, log_in <= 28; log_out = ceil(log2 n_gates).  ZKP_ERR_BAD_ARG, before anything is allocated: a
+ * NULL context or array, any other op (IllegalOperator), a node >= 2^log_in (IllegalNode), n_gates or log_in outside these rules.
+ * The host sorts the gates once (counting sort): natural order, grouped by left node and grouped by right node (gate order
+ * within a node's segment), and cuts every segment of more than 256 entries into chunks of 4096 (the long segments); then it
+ * uploads them.  About 24 n_gates + 8 * 2^log_in bytes of device memory.  The handle belongs to the context's device. */
+typedef struct zkp_gkr_layer zkp_gkr_layer;
+int32_t zkp_gkr_layer_upload(zkp_ctx* ctx, const uint8_t* op_host, const uint32_t* left_host, const uint32_t* right_host,
+                             size_t n_gates, uint32_t log_in, zkp_gkr_layer** layer);
+int32_t zkp_gkr_layer_free(zkp_ctx* ctx, zkp_gkr_layer* layer);
+/* info: n_gates, log_out, log_in, mul gates, largest fan-out by left node, by right node, long segments by left node, by right node */
+int32_t zkp_gkr_layer_info(const zkp_gkr_layer* layer, uint64_t info[8]);
+/* One layer of Circuit::evaluate (circuit.rs:140-185; hyrax/src/circuit.rs has the same gate model) with the padding of eval_output
+ * (evaluate.rs:16-21):  out[g] = op[g] ? in[left[g]] * in[right[g]] : in[left[g]] + in[right[g]]  for g < n_gates, out[g] = 0 for
+ * n_gates <= g < 2^log_out.  in_dev: 2^log_in Fr, out_dev: 2^log_out Fr (Montgomery, canonical, 16-byte aligned, device memory);
+ * they must not overlap.  One launch.  Returns when out_dev is written. */
+int32_t zkp_fr_gkr_eval_layer_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, const uint64_t* in_dev,
+                                  uint64_t* out_dev);
+/* The bookkeeping tables of one phase from ONE pass over the gates.  g_dev: 2^log_out Fr (G = alpha eq(gu) + beta eq(gv)),
+ * w_dev: 2^log_in Fr, out_dev: host array of 3 device pointers to 2^log_in Fr each.  With x = left[g], y = right[g]:
+ *   phase 1, eval_hg (evaluate.rs:79-99), w = V:        mul gates: out[0][x] += G[g] w[y]
+ *                                                       add gates: out[1][x] += G[g], out[2][x] += G[g] w[y]
+ *   phase 2, eval_fgu (evaluate.rs:101-119), w = eq(ru): mul gates: out[0][y] += G[g] w[x]
+ *                                                       add gates: out[1][y] += G[g] w[x];  out_dev[2] must be NULL
+ * Every slot of every output is written; a node without gates gets 0.  One field product per gate, no atomics: the thread that
+ * owns a node adds its segment; a long segment is added by one workgroup per chunk, then one workgroup per segment.  One launch
+ * when the layer has no long segment on that side (info[6] / info[7] == 0), three otherwise.
+ * ZKP_ERR_BAD_ARG, before anything is launched or written: a NULL or misaligned pointer, a phase other than 1 or 2, out_dev[2] != NULL
+ * in phase 2, an output that overlaps another output or an input.  ZKP_ERR_BAD_HANDLE: a layer of another device.
+ * Every element written is the canonical Montgomery representative (bit-exact results). */
+int32_t zkp_fr_gkr_tables_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, int32_t phase, const uint64_t* g_dev,
+                              const uint64_t* w_dev, uint64_t* const* out_dev);
+/* One round of phase_one_prover / phase_two_prover (libra/src/sumcheck.rs:21-97, 99-173; the ZK variants :186-426 run the same
+ * table work): bind the previous challenge into every table (combine_with_r, evaluate.rs:43-51) and evaluate the next round
+ * polynomial at t = 0 and t = 2 in ONE pass, plus one small launch that adds the per-workgroup partial sums.
+ *   phase 1: tables_dev = f, mul, add1, add2;  g = f (mul + add1) + add2;  fu_host is not read
+ *   phase 2: tables_dev = f, mul, add;         g = fu (mul f + add) + add f;  fu_host: one Fr (Montgomery, < r), host memory
+ * tables_dev: host array of 4 / 3 distinct device pointers, each to len Fr (Montgomery, 16-byte aligned), len a power of two.
+ * bind_host, the untouched elements [len/2, len), evals_out_host == NULL (bind only) and bind_host == NULL (round 0) are those of
+ * zkp_fr_sumcheck_round_dev; evals_out_host: 2 Fr (Montgomery), g(0) then g(2); g(1) is claim - g(0).
+ * ZKP_ERR_BAD_ARG, before anything runs: a phase other than 1 or 2, NULL or misaligned tables, tables that overlap, len not a power
+ * of two or > 2^28, len < 2 with bind_host, a length below 2 at evaluation time, both bind_host and evals_out_host NULL,
+ * *bind_host >= r, in phase 2 *fu_host >= r or a NULL fu_host with evals_out_host.
+ * Two launches for a call that evaluates, one for a bind-only call.  Returns after the evaluations are on the host. */
+int32_t zkp_fr_gkr_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t phase, uint64_t* const* tables_dev, size_t len,
+                             const uint64_t* fu_host, const uint64_t* bind_host, uint64_t* evals_out_host);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
