@@ -161,6 +161,9 @@ SIGNATURES = {
     "zkp_fr_gkr_eval_layer_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp]),
     "zkp_fr_gkr_tables_dev": (C.c_int32, [vp, C.c_int, vp, C.c_int32, vp, vp, vp]),
     "zkp_fr_gkr_round_dev": (C.c_int32, [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, vp]),
+    "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
+    "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+    "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_msm_g1_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g2_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g1_mont_batch_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, vp, vp, vp]),

@@ -347,6 +347,39 @@ class Context:
                    "zkp_fr_gkr_round_dev")
         return out
 
+    def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
+        """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
+        Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""
+        total = np.zeros(4, dtype=np.uint64) if want_total else None
+        _lib.check(self.lib.zkp_fr_prefix_product_dev(self.h, get_curve(curve).cid, C.c_void_p(in_ptr or 0), C.c_void_p(out_ptr or 0), n,
+                                                      _ptr(total)), "zkp_fr_prefix_product_dev")
+        return total
+
+    def fr_plonk_perm_z_dev(self, curve, w_ptrs, sigma_ptrs, log_n: int, ks, beta, gamma, z_out_ptr: int) -> bool:
+        """zkp_fr_plonk_perm_z_dev: the permutation accumulator z over 2^log_n rows into z_out.  w_ptrs / sigma_ptrs: 4 DEVICE
+        tables each; ks (4, 4), beta, gamma (4,): uint64 Montgomery.  Returns `closes` (z[n-1] perm[n-1] == 1)."""
+        assert len(w_ptrs) == 4 and len(sigma_ptrs) == 4
+        wa = (C.c_void_p * 4)(*[p or None for p in w_ptrs])
+        sa = (C.c_void_p * 4)(*[p or None for p in sigma_ptrs])
+        closes = C.c_int32(-1)
+        _lib.check(self.lib.zkp_fr_plonk_perm_z_dev(self.h, get_curve(curve).cid, wa, sa, log_n, _ptr(_c64(ks)), _ptr(_c64(beta)),
+                                                    _ptr(_c64(gamma)), C.c_void_p(z_out_ptr or 0), C.byref(closes)),
+                   "zkp_fr_plonk_perm_z_dev")
+        return closes.value == 1
+
+    def fr_plonk_quotient_dev(self, curve, w_ptrs, z_ptr: int, pi_ptr: int, q_ptrs, sigma_ptrs, l1_ptr: int, log_n: int, ks, beta,
+                              gamma, alpha, t_out_ptr: int):
+        """zkp_fr_plonk_quotient_dev: t = (t_arith + t_perm) v_4n_inversed over the 4 * 2^log_n coset points, one launch.
+        q_ptrs: q_0, q_1, q_2, q_3, q_m, q_c, q_arith.  Every table DEVICE Montgomery Fr; t_out overlaps no input."""
+        assert len(w_ptrs) == 4 and len(sigma_ptrs) == 4 and len(q_ptrs) == 7
+        wa = (C.c_void_p * 4)(*[p or None for p in w_ptrs])
+        sa = (C.c_void_p * 4)(*[p or None for p in sigma_ptrs])
+        qa = (C.c_void_p * 7)(*[p or None for p in q_ptrs])
+        _lib.check(self.lib.zkp_fr_plonk_quotient_dev(self.h, get_curve(curve).cid, wa, C.c_void_p(z_ptr or 0), C.c_void_p(pi_ptr or 0),
+                                                      qa, sa, C.c_void_p(l1_ptr or 0), log_n, _ptr(_c64(ks)), _ptr(_c64(beta)),
+                                                      _ptr(_c64(gamma)), _ptr(_c64(alpha)), C.c_void_p(t_out_ptr or 0)),
+                   "zkp_fr_plonk_quotient_dev")
+
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)
         xyz = _c64(xyz)

@@ -9,6 +9,7 @@
 #include "host_field.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
+#include "plonk.hpp"
 #include "spark.hpp"
 #include "sumcheck.hpp"
 
@@ -512,6 +513,33 @@ int32_t zkp_fr_gkr_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t phase, uin
                              const uint64_t* fu_host, const uint64_t* bind_host, uint64_t* evals_out_host) {
   if (!tables_dev || (!bind_host && !evals_out_host)) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { fr_gkr_round(ctx, curve, phase, tables_dev, len, fu_host, bind_host, evals_out_host); });
+}
+int32_t zkp_fr_prefix_product_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* in_dev, uint64_t* out_dev, size_t n,
+                                  uint64_t* total_out_host) {
+  if (!in_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_prefix_product(ctx, curve, in_dev, out_dev, n, total_out_host); });
+}
+int32_t zkp_fr_plonk_perm_z_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* const* w_dev, const uint64_t* const* sigma_dev,
+                                uint32_t log_n, const uint64_t* ks_host, const uint64_t* beta_host, const uint64_t* gamma_host,
+                                uint64_t* z_out_dev, int32_t* closes_out_host) {
+  if (!w_dev || !sigma_dev || !ks_host || !beta_host || !gamma_host || !z_out_dev || !closes_out_host) return ZKP_ERR_BAD_ARG;
+  for (int s = 0; s < 4; s++)
+    if (!w_dev[s] || !sigma_dev[s]) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_plonk_perm_z(ctx, curve, w_dev, sigma_dev, log_n, ks_host, beta_host, gamma_host, z_out_dev, closes_out_host); });
+}
+int32_t zkp_fr_plonk_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* const* w_4n, const uint64_t* z_4n,
+                                  const uint64_t* pi_4n, const uint64_t* const* q_4n, const uint64_t* const* sigma_4n,
+                                  const uint64_t* l1_4n, uint32_t log_n, const uint64_t* ks_host, const uint64_t* beta_host,
+                                  const uint64_t* gamma_host, const uint64_t* alpha_host, uint64_t* t_out_dev) {
+  if (!w_4n || !z_4n || !pi_4n || !q_4n || !sigma_4n || !l1_4n || !t_out_dev) return ZKP_ERR_BAD_ARG;
+  if (!ks_host || !beta_host || !gamma_host || !alpha_host) return ZKP_ERR_BAD_ARG;
+  for (int s = 0; s < 4; s++)
+    if (!w_4n[s] || !sigma_4n[s]) return ZKP_ERR_BAD_ARG;
+  for (int s = 0; s < 7; s++)
+    if (!q_4n[s]) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    fr_plonk_quotient(ctx, curve, w_4n, z_4n, pi_4n, q_4n, sigma_4n, l1_4n, log_n, ks_host, beta_host, gamma_host, alpha_host, t_out_dev);
+  });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

@@ -51,7 +51,8 @@ const char* zkp_status_string(int32_t status);
 /* "zkp_accel <major.minor> (gfx950)".  0.7.1: zkp_g1_ipa_fold_dev (IPA generator fold) / zkp_fr_dot_batch_dev (batched Fr inner
  * products); later in 0.7.1, detected by symbol: zkp_fr_sumcheck_round_dev (fused sum-check round) / zkp_fr_eq_evals_dev (eq
  * table), then zkp_fr_product_circuit_dev / zkp_fr_memcheck_circuits_dev (SPARK memory-checking hashes and product circuits),
- * then zkp_gkr_layer_upload / _free / _info and zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev (Libra GKR).
+ * then zkp_gkr_layer_upload / _free / _info and zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev (Libra GKR),
+ * then zkp_fr_prefix_product_dev / zkp_fr_plonk_perm_z_dev / zkp_fr_plonk_quotient_dev (PLONK rounds 2 and 3).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -339,6 +340,50 @@ int32_t zkp_fr_gkr_tables_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_lay
  * Two launches for a call that evaluates, one for a bind-only call.  Returns after the evaluations are on the host. */
 int32_t zkp_fr_gkr_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t phase, uint64_t* const* tables_dev, size_t len,
                              const uint64_t* fu_host, const uint64_t* bind_host, uint64_t* evals_out_host);
+/* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
+ * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
+ * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
+ * 16-byte aligned, device memory.  Scalars (*_host): Fr, Montgomery, < r, host memory.
+ *
+ * The exclusive running product:  out[0] = 1, out[i] = in[0] * ... * in[i-1]  for i < n;  *total_out_host (may be NULL) receives
+ * in[0] * ... * in[n-1].  1 <= n <= 2^30, any n.  out_dev may be in_dev itself; otherwise the two must not overlap.
+ * A workgroup owns a block of 1024 consecutive elements.  n <= 1024: one launch.  More: one launch leaves every block's total, the
+ * totals are scanned the same way (one more level per factor of 1024), one launch replays every block from its scanned total:
+ * 3 launches up to 2^20 elements, 5 above.  Separate launches on the context's stream: no kernel waits for another workgroup.
+ * ZKP_ERR_BAD_ARG, before anything runs: a NULL or misaligned vector, n outside the rule, vectors that overlap in part.
+ * Every element written is the canonical Montgomery representative (bit-exact results). */
+int32_t zkp_fr_prefix_product_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* in_dev, uint64_t* out_dev, size_t n,
+                                  uint64_t* total_out_host);
+/* PermutationKey::compute_z (plonk/src/ahp/indexer/permutation.rs:67-118) up to the evaluation vector z over domain_n, n = 2^log_n:
+ *   perm[i] = prod_j (w_j[i] + ks_j beta w^i + gamma) / prod_j (w_j[i] + beta sigma_j[i] + gamma),   z[0] = 1, z[i+1] = z[i] perm[i]
+ * with w = domain_n.element(1), the root zkp_ntt_dev uses for log_n.  w_dev / sigma_dev: host arrays of 4 device pointers to n Fr
+ * each (w_0..w_3 = aux, l, r, o of composer/arithmetic.rs; sigma_0..sigma_3 of composer/permutation.rs:62-83); ks_host: 4 Fr.
+ * The n inversions are ONE batch inversion (zkp_fr_batch_inverse_dev's kernel and convention: a zero denominator inverts to
+ * zero, where the reference panics at :99), the products zkp_fr_prefix_product_dev's launches over num[i] * (1 / den)[i].
+ * *closes_out_host = 1 when z[n-1] perm[n-1] == 1 (the assert_eq! of :112), else 0; the call returns ZKP_OK either way.
+ * Only z_out_dev[0 .. n) is written, last and from scratch memory: it may be one of the inputs.
+ * ZKP_ERR_BAD_ARG, before anything runs: a NULL or misaligned pointer, log_n < 2, a scalar >= r.  ZKP_ERR_DOMAIN_TOO_LARGE:
+ * log_n + 2 above the field's two-adicity (the 4n domain of the third round, PolynomialDegreeTooLarge). */
+int32_t zkp_fr_plonk_perm_z_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* const* w_dev, const uint64_t* const* sigma_dev,
+                                uint32_t log_n, const uint64_t* ks_host, const uint64_t* beta_host, const uint64_t* gamma_host,
+                                uint64_t* z_out_dev, int32_t* closes_out_host);
+/* The third-round quotient over the N = 4n points x_i = g w^i of the coset that ZKP_NTT_COSET_FFT evaluates on (g its coset
+ * generator, w = domain_4n.element(1)), ONE pass and one launch (prover.rs:184-202):
+ *   t[i] = (t_arith[i] + t_perm[i]) * v_4n_inversed[i]
+ *   t_arith[i] = (q_0 w_0 + q_1 w_1 + q_2 w_2 + q_3 w_3 + q_m w_1 w_2 + q_c + pi)[i] * q_arith[i]       (indexer/arithmetic.rs:107-114;
+ *                the q_arith.is_zero() branch is this product)
+ *   t_perm[i]  = (prod_j (w_j[i] + ks_j beta x_i + gamma) z[i] - prod_j (w_j[i] + beta sigma_j[i] + gamma) z[(i + 4) mod N]) alpha
+ *                + (z[i] - 1) l1[i] alpha^2                                                              (indexer/permutation.rs:155-166)
+ *   v_4n_inversed[i] = 1 / (x_i^n - 1) = 1 / (g^n (w^n)^(i mod 4) - 1): four values, computed on the host   (indexer/mod.rs:223-225)
+ * x_i (linear_4n, permutation.rs:134-137) is computed in the kernel.  w_4n / sigma_4n: host arrays of 4 device pointers, q_4n of
+ * 7 in the order q_0, q_1, q_2, q_3, q_m, q_c, q_arith; every table N Fr.  18 table reads and one write per point.
+ * t_out_dev must not overlap any input (point i + 4 of z is read by another thread than the one that writes point i).
+ * ZKP_ERR_BAD_ARG, before anything runs: a NULL or misaligned pointer, log_n < 2, a scalar >= r, t_out_dev overlapping an input.
+ * ZKP_ERR_DOMAIN_TOO_LARGE: log_n + 2 above the field's two-adicity. */
+int32_t zkp_fr_plonk_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* const* w_4n, const uint64_t* z_4n,
+                                  const uint64_t* pi_4n, const uint64_t* const* q_4n, const uint64_t* const* sigma_4n,
+                                  const uint64_t* l1_4n, uint32_t log_n, const uint64_t* ks_host, const uint64_t* beta_host,
+                                  const uint64_t* gamma_host, const uint64_t* alpha_host, uint64_t* t_out_dev);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
