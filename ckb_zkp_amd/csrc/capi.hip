@@ -11,6 +11,7 @@
 #include "ipa.hpp"
 #include "plonk.hpp"
 #include "spark.hpp"
+#include "stream_place.hpp"
 #include "sumcheck.hpp"
 
 using namespace zkp;
@@ -156,8 +157,12 @@ int32_t zkp_ctx_create_ex(zkp_ctx** out, int device_id, const zkp_ctx_config* us
     return ZKP_ERR_DEVICE;
   }
   // The proof pipeline keeps ~32 streams busy (8 lanes x 4); ROCm multiplexes HIP streams onto the hardware queues the
-  // runtime was given (GPU_MAX_HW_QUEUES) and streams that share a queue serialise.  The library does NOT touch the process
-  // environment: the queue count is the host's choice.
+  // runtime was given (GPU_MAX_HW_QUEUES), round-robin in stream-creation order, and streams that share a queue serialise.  The
+  // library does NOT touch the process environment: the queue count is the host's choice.  It only READS it, once, to decide in
+  // which order a lane creates its four streams (stream_place.hpp): with 1, 2 or 4 queues the roles are rotated by the lane index, so
+  // that the main streams of consecutive lanes sit on different queues and proof k + 1 does not queue behind the join of proof k;
+  // with any other count (8, 16, 32) the order is main, ws1, ws2, ws3 in every lane, the placement those counts were measured with.
+  // -DZKP_LANE_MAJOR_STREAMS builds the latter order for every count (A/B runs).
   zkp_ctx* ctx = new (std::nothrow) zkp_ctx();
   if (!ctx) return ZKP_ERR_OOM;
   ctx->device = device_id;
@@ -170,9 +175,24 @@ int32_t zkp_ctx_create_ex(zkp_ctx** out, int device_id, const zkp_ctx_config* us
     ZKP_HIP(hipEventCreate(&ctx->ev3));
     // (HIP stream priorities per role — high for the G2 chain and the B1 -> s*g_a + r*g1_b chain, whose reduction tails end a single
     //  proof — were measured in round 4 and lose everywhere: 8.2 -> 8.7-14 ms per single proof, 143 -> 90-133 pipelined proofs/s.)
+    const long long queues_env = env_num("GPU_MAX_HW_QUEUES", 4);
+    const int hw_queues = queues_env > 0 && queues_env <= 1024 ? (int)queues_env : 4;      // unset or <= 0: the runtime's default
     for (int l = 0; l < zkp_ctx::N_LANES; l++) {
       zkp_lane& L = ctx->lanes[l];
-      ZKP_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+      for (int slot = 0; slot < zkp_lane::N_WS; slot++) {
+#ifdef ZKP_LANE_MAJOR_STREAMS
+        const int role = slot;
+        (void)hw_queues;
+#else
+        const int role = stream_role_at(l, slot, zkp_lane::N_WS, hw_queues);
+#endif
+        if (role == 0) {                                      // the lane's main stream; ws[0] has none of its own
+          ZKP_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+        } else {
+          ZKP_HIP(hipStreamCreateWithFlags(&L.ws[role].stream, hipStreamNonBlocking));
+          L.ws[role].own_stream = true;
+        }
+      }
       ZKP_HIP(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming));
       ZKP_HIP(hipEventCreateWithFlags(&L.ev_a, hipEventDisableTiming));
       ZKP_HIP(hipEventCreateWithFlags(&L.ev_b1, hipEventDisableTiming));
@@ -182,10 +202,6 @@ int32_t zkp_ctx_create_ex(zkp_ctx** out, int device_id, const zkp_ctx_config* us
         ZKP_HIP(hipEventCreateWithFlags(&L.ws[i].sorted, hipEventDisableTiming));
         ZKP_HIP(hipEventCreateWithFlags(&L.ws[i].l1_done, hipEventDisableTiming));
         ZKP_HIP(hipEventCreateWithFlags(&L.ws[i].acc_done, hipEventDisableTiming));
-        if (i > 0) {
-          ZKP_HIP(hipStreamCreateWithFlags(&L.ws[i].stream, hipStreamNonBlocking));
-          L.ws[i].own_stream = true;
-        }
       }
     }
   });

@@ -1175,8 +1175,13 @@ void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint6
   const bool prof = ctx->profiling;
   ZKP_REQUIRE(pk->shard_world == 0, ZKP_ERR_BAD_ARG);
   size_t pending[zkp_ctx::N_LANES] = {};
-  // proofs in flight: 8 lanes x 4 streams = 2 streams per hardware queue (measured optimum at 2^20: 4 lanes 102, 6 lanes 103,
-  // 8 lanes 108-110, 12 lanes 104 proofs/s); 4 above 2^22 where a lane's scratch is tens of GB.  ZKP_LANES overrides.
+  // proofs in flight: 8 lanes x 4 streams = 2 streams per hardware queue with 16 queues, 8 with 4 (measured optimum at 2^20 and 16
+  // queues: 4 lanes 102, 6 lanes 103, 8 lanes 108-110, 12 lanes 104 proofs/s); 4 above 2^22 where a lane's scratch is tens of GB.
+  // ZKP_LANES overrides.  Consecutive proofs go to consecutive lanes, and which streams of lane l + 1 queue behind which of lane l is
+  // settled when the context creates them (capi.hip, stream_place.hpp): with 1, 2 or 4 hardware queues the main stream of lane l + 1
+  // shares its queue with ws1 of lane l, not with main of lane l, so the packets that open proof i + 1 do not wait behind the join,
+  // part 2 and read-back that close proof i (a kernel trace shows nothing of proof i + 1 starting before proof i
+  // has ended when all main streams share one queue).
   const int lanes_default = pk->log_n <= 22 ? 8 : 4;          // zkp_ctx_config.lanes / ZKP_LANES override it per context
   const int nl = std::max(1, std::min(ctx->cfg.lanes > 0 ? ctx->cfg.lanes : lanes_default, (int)zkp_ctx::N_LANES));
   auto select = [&](int l) {
