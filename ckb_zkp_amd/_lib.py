@@ -164,6 +164,8 @@ SIGNATURES = {
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+    "zkp_fr_poly_eval_many_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, vp, vp, vp]),
+    "zkp_fr_lincomb_dev": (C.c_int32, [vp, C.c_int, C.c_size_t, vp, vp, vp, vp, C.c_size_t]),
     "zkp_msm_g1_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g2_mont_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_msm_g1_mont_batch_dev": (C.c_int32, [vp, C.c_uint64, C.c_size_t, vp, vp, vp, vp]),

@@ -380,6 +380,30 @@ class Context:
                                                       _ptr(_c64(gamma)), _ptr(_c64(alpha)), C.c_void_p(t_out_ptr or 0)),
                    "zkp_fr_plonk_quotient_dev")
 
+    def fr_poly_eval_many_dev(self, curve, p_ptrs, ns, z) -> np.ndarray:
+        """zkp_fr_poly_eval_many_dev: the polynomials p_ptrs[k] (DEVICE Montgomery Fr, ns[k] coefficients; 0: the zero polynomial)
+        at ONE point z ((4,) uint64 Montgomery).  Returns the (count, 4) uint64 Montgomery evaluations."""
+        assert len(p_ptrs) == len(ns)
+        count = len(ns)
+        pa = (C.c_void_p * max(count, 1))(*[p or None for p in p_ptrs])
+        na = (C.c_size_t * max(count, 1))(*ns)
+        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        _lib.check(self.lib.zkp_fr_poly_eval_many_dev(self.h, get_curve(curve).cid, count, pa, na, _ptr(_c64(z)), _ptr(out)),
+                   "zkp_fr_poly_eval_many_dev")
+        return out[:count]
+
+    def fr_lincomb_dev(self, curve, p_ptrs, ns, coeffs, out_ptr: int, n_out: int):
+        """zkp_fr_lincomb_dev: out[i] = sum_{k : i < ns[k]} coeffs[k] p_k[i] for i < n_out, one launch.  p_ptrs / out: DEVICE
+        Montgomery Fr; coeffs: (count, 4) uint64 Montgomery.  out may be one of the inputs itself."""
+        assert len(p_ptrs) == len(ns)
+        count = len(ns)
+        pa = (C.c_void_p * max(count, 1))(*[p or None for p in p_ptrs])
+        na = (C.c_size_t * max(count, 1))(*ns)
+        ca = _c64(coeffs) if count else np.zeros((1, 4), dtype=np.uint64)
+        assert ca.size == 4 * max(count, 1)
+        _lib.check(self.lib.zkp_fr_lincomb_dev(self.h, get_curve(curve).cid, count, pa, na, _ptr(ca), C.c_void_p(out_ptr or 0), n_out),
+                   "zkp_fr_lincomb_dev")
+
     def fold(self, curve, group: int, xyz: np.ndarray) -> np.ndarray:
         c = get_curve(curve)
         xyz = _c64(xyz)

@@ -9,6 +9,7 @@
 #include "host_field.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
+#include "fr_open.hpp"
 #include "plonk.hpp"
 #include "spark.hpp"
 #include "stream_place.hpp"
@@ -556,6 +557,20 @@ int32_t zkp_fr_plonk_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_
   return guarded(ctx, [&] {
     fr_plonk_quotient(ctx, curve, w_4n, z_4n, pi_4n, q_4n, sigma_4n, l1_4n, log_n, ks_host, beta_host, gamma_host, alpha_host, t_out_dev);
   });
+}
+int32_t zkp_fr_poly_eval_many_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* p_dev, const size_t* ns,
+                                  const uint64_t* z_host, uint64_t* out_host) {
+  if (!ctx || !p_dev || !ns || !z_host || !out_host) return ZKP_ERR_BAD_ARG;
+  for (size_t k = 0; k < count && k < FR_OPEN_MAX_POLYS; k++)
+    if (ns[k] && !p_dev[k]) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_poly_eval_many(ctx, curve, count, p_dev, ns, z_host, out_host); });
+}
+int32_t zkp_fr_lincomb_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* p_dev, const size_t* ns,
+                           const uint64_t* coeffs_host, uint64_t* out_dev, size_t n_out) {
+  if (!ctx || !p_dev || !ns || !coeffs_host || !out_dev) return ZKP_ERR_BAD_ARG;
+  for (size_t k = 0; k < count && k < FR_OPEN_MAX_POLYS; k++)
+    if (ns[k] && !p_dev[k]) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_lincomb(ctx, curve, count, p_dev, ns, coeffs_host, out_dev, n_out); });
 }
 int32_t zkp_msm_g1_mont_batch_dev(zkp_ctx* ctx, uint64_t h, size_t count, const size_t* offsets,
                                   const uint64_t* const* scalars_dev, const size_t* ns, uint64_t* out_xyz) {

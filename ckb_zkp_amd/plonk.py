@@ -5,7 +5,13 @@ The rounds produce every polynomial the prover commits: w_0..w_3, z and t_0..t_3
 (interpolate = ifft over domain_n, then coset_fft over domain_4n of the zero-padded coefficients) and one fused call:
 zkp_fr_plonk_perm_z_dev in round 2, zkp_fr_plonk_quotient_dev in round 3.  Commitments, openings and the transcript are the
 caller's: the challenges beta, gamma and alpha are passed in.  Field elements are canonical Python integers; device tables are
-Montgomery Fr.  A coefficient vector always has n entries (the reference drops trailing zeros)."""
+Montgomery Fr.  A coefficient vector always has n entries (the reference drops trailing zeros).
+
+After round 3 (Plonk::prove, plonk/src/lib.rs:93-204): prover_fourth_round evaluates the 20 coefficient vectors at zeta in ONE
+zkp_fr_poly_eval_many_dev call (and z at zeta w in a second) and derives the eleven evaluations of
+AHPForPLONK::construct_linear_combinations (ahp/mod.rs:29-113); prover_openings builds each opening polynomial with ONE
+zkp_fr_lincomb_dev call and zkp_poly_div_linear_dev; prove() strings the rounds together with non-hiding KZG10 commitments and the
+caller's transcript.  The Fiat-Shamir transcript of plonk/src/rng.rs and the verifier's pairing check are not here."""
 from __future__ import annotations
 
 import numpy as np
@@ -19,8 +25,17 @@ PLONK_SCAN_ITEMS = 4          # elements per thread
 PLONK_SCAN_BLOCK = 1024       # elements per workgroup; more than one block: the totals are scanned as a level of their own
 PLONK_QUOT_THREADS = 256      # the quotient kernel's grid is capped at THREADS * MAX_BLOCKS threads; each strides over its points
 PLONK_QUOT_MAX_BLOCKS = 512
+FR_OPEN_MAX_POLYS = 32        # csrc/fr_open.hpp: vectors per zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev call
+FR_OPEN_EVAL_THREADS = 256    # the evaluation's grid is capped like the quotient's: THREADS * MAX_BLOCKS threads, each strides
+FR_OPEN_EVAL_MAX_BLOCKS = 512
+FR_OPEN_EVAL_GROUP = 4        # polynomials that share one walk of the powers of z (their accumulators stay in registers)
 
 SELECTORS = ("q_0", "q_1", "q_2", "q_3", "q_m", "q_c", "q_arith", "sigma_0", "sigma_1", "sigma_2", "sigma_3")
+PROVER_POLYS = ("w_0", "w_1", "w_2", "w_3", "z", "t_0", "t_1", "t_2", "t_3")     # AHPForPLONK::LABELS (ahp/mod.rs:26-27)
+BASE_POLYS = PROVER_POLYS + SELECTORS                                            # the 20 vectors of n coefficients
+# the eleven linear combinations in the order Plonk::prove sends their evaluations (lib.rs:171-183 sorts by label)
+EVAL_LABELS = ("q_arith", "r", "sigma_0", "sigma_1", "sigma_2", "t", "w_0", "w_1", "w_2", "w_3", "z")
+ZETA_LABELS = tuple(k for k in EVAL_LABELS if k != "z")                          # queried at zeta; z is queried at zeta w
 
 
 def domain_generator(curve, log_n: int) -> int:
@@ -119,8 +134,9 @@ class Index:
     """AHPForPLONK::index on the device: the 11 selector vectors over the 4n coset (ifft over domain_n, coset_fft over domain_4n),
     sigma_0..sigma_3 over domain_n (compute_z reads them) and l1_4n.  close() frees every buffer."""
 
-    def __init__(self, ctx, curve, selectors: dict, ks):
-        """selectors: Composer.compose(ks), or the same keys with (n, 4) uint64 Montgomery arrays"""
+    def __init__(self, ctx, curve, selectors: dict, ks, keep_coeffs: bool = False):
+        """selectors: Composer.compose(ks), or the same keys with (n, 4) uint64 Montgomery arrays.  keep_coeffs: also keep the n
+        coefficients of the 11 selector polynomials (coeffs[name]): rounds 4 and 5 evaluate and open them."""
         self.ctx, self.curve = ctx, get_curve(curve)
         c = self.curve
         self.ks = [k % c.r for k in ks]
@@ -131,7 +147,7 @@ class Index:
         if self.log_n + 2 > c.two_adicity:
             raise ValueError("PolynomialDegreeTooLarge")
         self.bufs = []
-        self.on_4n, self.sigma_n = {}, []
+        self.on_4n, self.sigma_n, self.coeffs = {}, [], {}
         try:
             for name in SELECTORS:
                 evals = _as_mont(selectors[name], c)
@@ -142,7 +158,9 @@ class Index:
                     keep = self._alloc(self.n)
                     ctx.d2d(keep, d, 32 * self.n)
                     self.sigma_n.append(keep)
-                extend_in_place(ctx, c, d, self.log_n)
+                if keep_coeffs:
+                    self.coeffs[name] = self._alloc(self.n)
+                extend_in_place(ctx, c, d, self.log_n, self.coeffs.get(name))
                 self.on_4n[name] = d
             l1 = np.zeros((self.n, 4), dtype=np.uint64)                # first_lagrange_poly (utils.rs:39-43)
             l1[0] = fr_mont(1, c)
@@ -171,7 +189,7 @@ class Index:
             self.ctx.sync()
         for d in bufs:
             self.ctx.dev_free(d)
-        self.on_4n, self.sigma_n, self.l1_4n = {}, [], None
+        self.on_4n, self.sigma_n, self.l1_4n, self.coeffs = {}, [], None, {}
 
 
 def _as_mont(v, c) -> np.ndarray:
@@ -209,7 +227,9 @@ class ProverState:
         self.coeffs["z"] = self._alloc(n)
         for k in range(4):
             self.coeffs[f"t_{k}"] = self.t + 32 * n * k               # quad_split: consecutive chunks of n coefficients
-        self.beta = self.gamma = None
+        self.beta = self.gamma = self.alpha = self.zeta = None
+        self.base_evals = self.evals = self.terms = None              # round 4: the 21 base evaluations, the eleven, r's terms
+        self.open_tmp = self.w_zeta = self.w_shifted = None           # round 5 (allocated on first use)
         self.round = 0
 
     def _alloc(self, elems: int) -> int:
@@ -284,6 +304,193 @@ def prover_third_round(ps: ProverState, alpha: int, to_host: bool = True):
     ctx.fr_plonk_quotient_dev(c, ps.w_4n, ps.z_4n, ps.pi_4n, ix.q_ptrs(), ix.sigma_ptrs(), ix.l1_4n, ix.log_n, fr_to_mont(ix.ks, c),
                               fr_mont(ps.beta, c), fr_mont(ps.gamma, c), fr_mont(alpha % c.r, c), ps.t)
     ctx.ntt_dev(c, ps.t, ix.log_n + 2, NTT_COSET_IFFT)
+    ps.alpha = alpha % c.r
     ps.round = 3
     names = [f"t_{k}" for k in range(4)]
     return [ps.read(k) for k in names] if to_host else [ps.coeffs[k] for k in names]
+
+
+# ------------------------------------------------------------------------------- evaluations, linearisation, openings
+def first_lagrange_at(n: int, zeta: int, r: int) -> int:
+    """evaluate_first_lagrange_poly (utils.rs:45-50)"""
+    return (pow(zeta, n, r) - 1) * pow(n * (zeta - 1), -1, r) % r
+
+
+def linearisation_terms(curve, n: int, ks, base: dict, beta: int, gamma: int, alpha: int, zeta: int) -> list:
+    """The eight (scalar, label) terms of r: ArithmeticKey::construct_linear_combination (indexer/arithmetic.rs:22-38) plus
+    PermutationKey::construct_linear_combination (indexer/permutation.rs:32-65), signs as written there.  base: the evaluations
+    of w_0..w_3, q_arith, sigma_0..sigma_2 at zeta and "z_shifted" = z(zeta w).  Host only."""
+    r = get_curve(curve).r
+    w = [base[f"w_{j}"] for j in range(4)]
+    qa = base["q_arith"]
+    terms = [(qa * w[0] % r, "q_0"), (qa * w[1] % r, "q_1"), (qa * w[2] % r, "q_2"), (qa * w[3] % r, "q_3"),
+             (qa * w[1] % r * w[2] % r, "q_m"), (qa, "q_c")]
+    numerator = 1
+    for j in range(4):
+        numerator = numerator * (w[j] + ks[j] * beta % r * zeta + gamma) % r
+    denumerator = beta * base["z_shifted"] % r
+    for j in range(3):
+        denumerator = denumerator * (w[j] + beta * base[f"sigma_{j}"] + gamma) % r
+    alpha_2 = alpha * alpha % r
+    terms.append(((numerator * alpha + first_lagrange_at(n, zeta, r) * alpha_2) % r, "z"))
+    terms.append((-denumerator * alpha % r, "sigma_3"))
+    return terms
+
+
+def prover_fourth_round(ps: ProverState, zeta: int) -> dict:
+    """The evaluations Plonk::prove sends (lib.rs:143-183), keyed and ordered as EVAL_LABELS: ONE zkp_fr_poly_eval_many_dev call
+    at zeta over the 20 base polynomials, one more for z at zeta w; t = sum zeta^(kn) t_k(zeta) and r(zeta) follow on the host by
+    linearity.  The 21 base evaluations stay in ps.base_evals ("z_shifted": z at zeta w), r's terms in ps.terms."""
+    ix, ctx, c = ps.index, ps.ctx, ps.index.curve
+    assert ps.round >= 3
+    if len(ix.coeffs) != len(SELECTORS):
+        raise ValueError("round 4 needs the selector coefficients: build the Index with keep_coeffs=True")
+    n, r = ix.n, c.r
+    zeta %= r
+    ptrs = [ps.coeffs[k] for k in PROVER_POLYS] + [ix.coeffs[k] for k in SELECTORS]
+    at_zeta = fr_from_mont(ctx.fr_poly_eval_many_dev(c, ptrs, [n] * len(ptrs), fr_mont(zeta, c)), c)
+    shifted = zeta * domain_generator(c, ix.log_n) % r
+    base = dict(zip(BASE_POLYS, at_zeta))
+    base["z_shifted"] = fr_from_mont(ctx.fr_poly_eval_many_dev(c, [ps.coeffs["z"]], [n], fr_mont(shifted, c)), c)[0]
+    terms = linearisation_terms(c, n, ix.ks, base, ps.beta, ps.gamma, ps.alpha, zeta)
+    zn = pow(zeta, n, r)
+    evals = {k: base[k] for k in EVAL_LABELS if k in base}
+    evals["z"] = base["z_shifted"]
+    evals["t"] = sum(pow(zn, k, r) * base[f"t_{k}"] for k in range(4)) % r
+    evals["r"] = sum(s * base[label] for s, label in terms) % r
+    ps.zeta, ps.base_evals, ps.terms = zeta, base, terms
+    ps.evals = {k: evals[k] for k in EVAL_LABELS}
+    ps.round = 4
+    return dict(ps.evals)
+
+
+def _lincomb(ps: ProverState, terms, out_ptr: int):
+    """out = sum scalar * polynomial(label) over n coefficients: ONE zkp_fr_lincomb_dev call"""
+    ix, c = ps.index, ps.index.curve
+    at = lambda label: ps.coeffs[label] if label in ps.coeffs else ix.coeffs[label]      # noqa: E731
+    ps.ctx.fr_lincomb_dev(c, [at(label) for _, label in terms], [ix.n] * len(terms), fr_to_mont([s % c.r for s, _ in terms], c), out_ptr,
+                          ix.n)
+
+
+def linearisation_poly(ps: ProverState, terms, out_ptr: int):
+    """the n coefficients of r = sum scalar * label (terms: linearisation_terms) into out_ptr, one zkp_fr_lincomb_dev call"""
+    if len(ps.index.coeffs) != len(SELECTORS):
+        raise ValueError("the linearisation polynomial needs the selector coefficients: build the Index with keep_coeffs=True")
+    _lincomb(ps, terms, out_ptr)
+
+
+def verifier_equality_check(curve, n: int, evals: dict, public_inputs, beta: int, gamma: int, alpha: int, zeta: int) -> bool:
+    """verifier_equality_check (ahp/verifier.rs:101-150) on the eleven evaluations.  pi(zeta) is taken in Lagrange form over the
+    non-zero public inputs: sum pi_i w^i (zeta^n - 1) / (n (zeta - w^i)).  Host only."""
+    c = get_curve(curve)
+    r = c.r
+    v_zeta = (pow(zeta, n, r) - 1) % r
+    w = domain_generator(c, n.bit_length() - 1)
+    pi_zeta, wi = 0, 1
+    for v in public_inputs:
+        if v % r:
+            pi_zeta += v * wi % r * v_zeta % r * pow(n * (zeta - wi), -1, r)
+        wi = wi * w % r
+    prod = evals["z"] * (evals["w_3"] + gamma) % r
+    for j in range(3):
+        prod = prod * (evals[f"w_{j}"] + beta * evals[f"sigma_{j}"] + gamma) % r
+    lhs = evals["t"] * v_zeta % r
+    rhs = (evals["r"] + evals["q_arith"] * pi_zeta - prod * alpha - first_lagrange_at(n, zeta, r) * alpha * alpha) % r
+    return lhs == rhs
+
+
+def opening_weights(curve, epsilon: int) -> dict:
+    """epsilon^j over the labels queried at zeta in ascending order, starting at epsilon^0: how ark-poly-commit 0.2's
+    open_combinations batches the linear combinations of one point [recalled, unverifiable offline: the crate is not in the
+    reference tree]"""
+    r = get_curve(curve).r
+    return {label: pow(epsilon, j, r) for j, label in enumerate(ZETA_LABELS)}
+
+
+def zeta_opening_terms(ps: ProverState, weights: dict) -> list:
+    """sum_label weights[label] * LC_label over ZETA_LABELS as (scalar, base polynomial) terms: the LCs t and r are expanded into
+    their terms, so each of the 20 base polynomials appears once and no LC polynomial is materialised"""
+    r, n = ps.index.curve.r, ps.index.n
+    zn = pow(ps.zeta, n, r)
+    acc = dict.fromkeys(BASE_POLYS, 0)
+    for label in ZETA_LABELS:
+        wgt = weights[label] % r
+        if label == "t":
+            for k in range(4):
+                acc[f"t_{k}"] += wgt * pow(zn, k, r)
+        elif label == "r":
+            for s, name in ps.terms:
+                acc[name] += wgt * s
+        else:
+            acc[label] += wgt
+    return [(acc[k] % r, k) for k in BASE_POLYS]
+
+
+def prover_openings(ps: ProverState, zeta: int, weights: dict | None = None, epsilon: int | None = None, to_host: bool = True):
+    """The two opening polynomials of PC::open_combinations for verifier_query_set (ahp/verifier.rs:77-99):
+        W_zeta = (sum_label weights[label] * LC_label) / (X - zeta)  over the ten labels queried at zeta (ZETA_LABELS),
+        W_shifted_zeta = z / (X - zeta w).
+    W_zeta is ONE zkp_fr_lincomb_dev call over the 20 base polynomials (zeta_opening_terms), then zkp_poly_div_linear_dev;
+    W_shifted_zeta divides z directly.  Each has n - 1 coefficients and stays on the device (ps.w_zeta, ps.w_shifted).
+    weights: label -> integer.  Without weights, epsilon gives opening_weights(): epsilon^j over the labels in ascending order
+    from epsilon^0, as ark-poly-commit 0.2's open_combinations does [recalled, unverifiable offline].
+    Returns (W_zeta, W_shifted_zeta) as coefficient lists (to_host) or device pointers."""
+    ix, ctx, c = ps.index, ps.ctx, ps.index.curve
+    assert ps.round >= 4 and zeta % c.r == ps.zeta
+    if weights is None:
+        if epsilon is None:
+            raise ValueError("weights or epsilon")
+        weights = opening_weights(c, epsilon)
+    n = ix.n
+    if ps.open_tmp is None:
+        ps.open_tmp, ps.w_zeta, ps.w_shifted = ps._alloc(n), ps._alloc(n), ps._alloc(n)
+    _lincomb(ps, zeta_opening_terms(ps, weights), ps.open_tmp)
+    ctx.poly_div_linear(c, ps.open_tmp, n, fr_mont(ps.zeta, c), ps.w_zeta)
+    ctx.poly_div_linear(c, ps.coeffs["z"], n, fr_mont(ps.zeta * domain_generator(c, ix.log_n) % c.r, c), ps.w_shifted)
+    ps.round = 5
+    if not to_host:
+        return ps.w_zeta, ps.w_shifted
+    out = []
+    for d in (ps.w_zeta, ps.w_shifted):
+        a = np.zeros((n - 1, 4), dtype=np.uint64)
+        ctx.d2h(a, d)
+        out.append(fr_from_mont(a, c))
+    return tuple(out)
+
+
+def _commit(ctx, ck, c, d: int, count: int):
+    """non-hiding KZG10 commitment to `count` coefficients on the device (to_labeled, utils.rs:61-63: no hiding bound, no
+    degree bound) as an affine canonical point (None: the identity)"""
+    from .codec import g1_from_mont
+    xy, inf = ctx.into_affine(c, 1, ck.powers_of_g.msm_mont_dev(d, count))
+    return g1_from_mont(xy, [inf], c)[0]
+
+
+def prove(ctx, ck, index: Index, witnesses, public_inputs, challenge) -> dict:
+    """Plonk::prove (lib.rs:93-204) without its transcript: rounds 1-3, the commitments, round 4 and the openings.
+    ck: a kzg10.CommitterKey with at least n powers.  challenge(stage, payload) is the caller's transcript: stage 1 -> (beta, gamma)
+    after the commitments to w_0..w_3, 2 -> alpha after z, 3 -> zeta after t_0..t_3 (payload: the commitments so far), 4 -> epsilon
+    after the evaluations (payload: the evaluations).  Returns {"commitments": label -> point for the nine prover polynomials,
+    "evaluations": the eleven in the reference's order, "witnesses": (commitment to W_zeta, to W_shifted_zeta)}; points are affine
+    canonical (x, y), None for the identity."""
+    c, n = index.curve, index.n
+    if ck.supported_degree + 1 < n:
+        raise ValueError("the committer key has fewer than n powers")
+    ps = prover_init(index, public_inputs)
+    try:
+        comms = {}
+        for k, d in zip(PROVER_POLYS[:4], prover_first_round(ps, witnesses, to_host=False)):
+            comms[k] = _commit(ctx, ck, c, d, n)
+        beta, gamma = challenge(1, dict(comms))
+        comms["z"] = _commit(ctx, ck, c, prover_second_round(ps, beta, gamma, to_host=False), n)
+        alpha = challenge(2, dict(comms))
+        for k, d in zip(PROVER_POLYS[5:], prover_third_round(ps, alpha, to_host=False)):
+            comms[k] = _commit(ctx, ck, c, d, n)
+        zeta = challenge(3, dict(comms))
+        evals = prover_fourth_round(ps, zeta)
+        epsilon = challenge(4, dict(evals))
+        w_zeta, w_shifted = prover_openings(ps, zeta, epsilon=epsilon, to_host=False)
+        wit = (_commit(ctx, ck, c, w_zeta, n - 1), _commit(ctx, ck, c, w_shifted, n - 1))
+    finally:
+        ps.close()
+    return {"commitments": comms, "evaluations": evals, "witnesses": wit}

@@ -52,7 +52,8 @@ const char* zkp_status_string(int32_t status);
  * products); later in 0.7.1, detected by symbol: zkp_fr_sumcheck_round_dev (fused sum-check round) / zkp_fr_eq_evals_dev (eq
  * table), then zkp_fr_product_circuit_dev / zkp_fr_memcheck_circuits_dev (SPARK memory-checking hashes and product circuits),
  * then zkp_gkr_layer_upload / _free / _info and zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev (Libra GKR),
- * then zkp_fr_prefix_product_dev / zkp_fr_plonk_perm_z_dev / zkp_fr_plonk_quotient_dev (PLONK rounds 2 and 3).
+ * then zkp_fr_prefix_product_dev / zkp_fr_plonk_perm_z_dev / zkp_fr_plonk_quotient_dev (PLONK rounds 2 and 3),
+ * then zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev (PLONK evaluations and opening polynomials).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -384,6 +385,32 @@ int32_t zkp_fr_plonk_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_
                                   const uint64_t* pi_4n, const uint64_t* const* q_4n, const uint64_t* const* sigma_4n,
                                   const uint64_t* l1_4n, uint32_t log_n, const uint64_t* ks_host, const uint64_t* beta_host,
                                   const uint64_t* gamma_host, const uint64_t* alpha_host, uint64_t* t_out_dev);
+/* PLONK evaluations and opening polynomials (later in 0.7.1, detected by symbol): what Plonk::prove (plonk/src/lib.rs:93-204)
+ * does with the coefficient vectors of rounds 1-3.  Rules common to both entries: 1 <= count <= 32; p_dev and ns are host arrays
+ * of `count` device pointers and lengths; every ns[k] <= 2^30; ns[k] == 0 is the zero polynomial and its pointer may be NULL.
+ * Vectors: Fr, Montgomery, canonical, 16-byte aligned, device memory.  Scalars (*_host): Fr, Montgomery, < r, host memory.
+ * Every element written is the canonical Montgomery representative (bit-exact results); inputs are never written.
+ * ZKP_ERR_BAD_ARG is returned before anything runs and with every output untouched.
+ *
+ * out_host[k] = sum_{i < ns[k]} p_k[i] z^i  for `count` polynomials at ONE point z (EvaluationsProvider::get_lc_eval,
+ * plonk/src/ahp/evaluations.rs:24-49, one label at a time); out_host: count Fr.  The same pointer may appear more than once.
+ * One pass reads every coefficient once with consecutive 16-byte loads: thread j of T = 256 * min(ceil(max ns / 256), 512)
+ * owns the indices j, j + T, ..., forms z^j once and steps by z^T; the polynomials are walked in register groups of 4.
+ * Two launches (the pass, then one workgroup per polynomial adds its partials), one copy back, one synchronise: the call
+ * returns after the evaluations are on the host.  z == 0 gives p_k[0].
+ * ZKP_ERR_BAD_ARG: count outside the rule, a length above 2^30, a NULL or misaligned vector with ns[k] > 0, *z_host >= r. */
+int32_t zkp_fr_poly_eval_many_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* p_dev, const size_t* ns,
+                                  const uint64_t* z_host, uint64_t* out_host);
+/* out[i] = sum_{k : i < ns[k]} c_k p_k[i],  i < n_out   (the polynomial of an ark_poly_commit LinearCombination); coeffs_host:
+ * count Fr.  One element-wise launch; the scalars and the pointer / length table travel as kernel arguments.  A term whose
+ * scalar is zero (or whose length is 0) is dropped on the host; if every term is dropped, out is zero-filled.  1 <= n_out <= 2^30
+ * and every ns[k] <= n_out.  out_dev may be one of the p_dev[k] itself (same base: index i is read before it is written and no
+ * other index is touched); any other overlap of out_dev[0 .. n_out) with p_dev[k][0 .. ns[k]) is rejected.
+ * Launches only, like zkp_fr_vec_op_dev: the result is ordered before later work on the context's stream.
+ * ZKP_ERR_BAD_ARG: count or n_out outside the rule, ns[k] > n_out, a NULL or misaligned vector, out_dev overlapping an input
+ * in part, a scalar >= r. */
+int32_t zkp_fr_lincomb_dev(zkp_ctx* ctx, zkp_curve_t curve, size_t count, const uint64_t* const* p_dev, const size_t* ns,
+                           const uint64_t* coeffs_host, uint64_t* out_dev, size_t n_out);
 /* KZG10::commit / open (marlin/src/pc/kzg10.rs:108-109,137-140): MSM of Montgomery Fr coefficients that are already
  * on the DEVICE against powers[offset ..] (offset = number of skipped leading zeros) */
 int32_t zkp_msm_g1_mont_dev(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* fr_scalars_dev, size_t n,
