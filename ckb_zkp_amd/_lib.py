@@ -161,6 +161,8 @@ SIGNATURES = {
     "zkp_fr_gkr_eval_layer_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp]),
     "zkp_fr_gkr_tables_dev": (C.c_int32, [vp, C.c_int, vp, C.c_int32, vp, vp, vp]),
     "zkp_fr_gkr_round_dev": (C.c_int32, [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, vp]),
+    "zkp_fr_gkr_eval_layer_batch_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, C.c_size_t]),
+    "zkp_fr_gkr_dp_round_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

@@ -347,6 +347,25 @@ class Context:
                    "zkp_fr_gkr_round_dev")
         return out
 
+    def fr_gkr_eval_layer_batch_dev(self, curve, layer: int, in_ptr: int, out_ptr: int, n: int):
+        """zkp_fr_gkr_eval_layer_batch_dev: one layer over n copies, node-major DEVICE Montgomery Fr: out[g n + t] =
+        in[left n + t] (+ or *) in[right n + t], zero rows up to 2^log_out"""
+        _lib.check(self.lib.zkp_fr_gkr_eval_layer_batch_dev(self.h, get_curve(curve).cid, C.c_void_p(layer), C.c_void_p(in_ptr or 0),
+                                                            C.c_void_p(out_ptr or 0), n), "zkp_fr_gkr_eval_layer_batch_dev")
+
+    def fr_gkr_dp_round_dev(self, curve, layer: int, v_ptr: int, eq_ptr: int, w_ptr: int, n: int, length: int, bind=None,
+                            want_evals: bool = True, finals_ptr: int = 0):
+        """zkp_fr_gkr_dp_round_dev: one round of Hyrax's sum-check over the copies.  v: 2^log_in rows of stride n, eq: n, w: 2^log_out
+        DEVICE Montgomery Fr; `length` live.  bind: one Montgomery Fr bound into every row and eq first (length halves), or None.
+        finals_ptr: 2^log_in Fr that receive element 0 of every row (only when the bound length is 1).
+        Returns the (3, 4) uint64 Montgomery g(0), g(2), g(3), or None without want_evals."""
+        x = None if bind is None else _c64(bind)
+        out = np.zeros((3, 4), dtype=np.uint64) if want_evals else None
+        _lib.check(self.lib.zkp_fr_gkr_dp_round_dev(self.h, get_curve(curve).cid, C.c_void_p(layer), C.c_void_p(v_ptr or 0),
+                                                    C.c_void_p(eq_ptr or 0), C.c_void_p(w_ptr or 0), n, length, _ptr(x), _ptr(out),
+                                                    C.c_void_p(finals_ptr or 0)), "zkp_fr_gkr_dp_round_dev")
+        return out
+
     def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
         """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
         Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""

@@ -7,6 +7,7 @@
 #include "ctx.hpp"
 #include "gkr.hpp"
 #include "host_field.hpp"
+#include "hyrax.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
 #include "fr_open.hpp"
@@ -530,6 +531,17 @@ int32_t zkp_fr_gkr_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t phase, uin
                              const uint64_t* fu_host, const uint64_t* bind_host, uint64_t* evals_out_host) {
   if (!tables_dev || (!bind_host && !evals_out_host)) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { fr_gkr_round(ctx, curve, phase, tables_dev, len, fu_host, bind_host, evals_out_host); });
+}
+int32_t zkp_fr_gkr_eval_layer_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, const uint64_t* in_dev,
+                                        uint64_t* out_dev, size_t n) {
+  if (!layer || !in_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_gkr_eval_layer_batch(ctx, curve, layer, in_dev, out_dev, n); });
+}
+int32_t zkp_fr_gkr_dp_round_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, uint64_t* v_dev, uint64_t* eq_dev,
+                                const uint64_t* w_dev, size_t n, size_t len, const uint64_t* bind_host, uint64_t* evals_out_host,
+                                uint64_t* finals_dev) {
+  if (!layer || !v_dev || !eq_dev || !w_dev || (!bind_host && !evals_out_host)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_gkr_dp_round(ctx, curve, layer, v_dev, eq_dev, w_dev, n, len, bind_host, evals_out_host, finals_dev); });
 }
 int32_t zkp_fr_prefix_product_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* in_dev, uint64_t* out_dev, size_t n,
                                   uint64_t* total_out_host) {

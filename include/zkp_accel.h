@@ -53,7 +53,8 @@ const char* zkp_status_string(int32_t status);
  * table), then zkp_fr_product_circuit_dev / zkp_fr_memcheck_circuits_dev (SPARK memory-checking hashes and product circuits),
  * then zkp_gkr_layer_upload / _free / _info and zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev (Libra GKR),
  * then zkp_fr_prefix_product_dev / zkp_fr_plonk_perm_z_dev / zkp_fr_plonk_quotient_dev (PLONK rounds 2 and 3),
- * then zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev (PLONK evaluations and opening polynomials).
+ * then zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev (PLONK evaluations and opening polynomials),
+ * then zkp_fr_gkr_eval_layer_batch_dev / zkp_fr_gkr_dp_round_dev (Hyrax data-parallel GKR).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -341,6 +342,44 @@ int32_t zkp_fr_gkr_tables_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_lay
  * Two launches for a call that evaluates, one for a bind-only call.  Returns after the evaluations are on the host. */
 int32_t zkp_fr_gkr_round_dev(zkp_ctx* ctx, zkp_curve_t curve, int32_t phase, uint64_t* const* tables_dev, size_t len,
                              const uint64_t* fu_host, const uint64_t* bind_host, uint64_t* evals_out_host);
+/* Hyrax's data-parallel GKR (later in 0.7.1, detected by symbol): n copies of one layered circuit proved at once, the table work of
+ * one layer in the loop of HyraxProof::prover (hyrax/src/hyrax_proof.rs:92-147).  The wiring is a zkp_gkr_layer (hyrax/src/circuit.rs
+ * has Libra's gate model).  Pedersen and packing commitments, blinds and the transcript stay with the caller.
+ * A layer's values over all copies are NODE-MAJOR: V[i n + t] is node i in copy t, i < 2^log_in, n a power of two,
+ * log_in + log2 n <= 28; Fr, Montgomery, canonical, 16-byte aligned, device memory.
+ *
+ * One layer of Circuit::evaluate (hyrax/src/circuit.rs:115-163) over n copies, with the zero rows of hyrax_proof.rs:104-107:
+ *   out[g n + t] = op[g] ? in[left[g] n + t] * in[right[g] n + t] : in[left[g] n + t] + in[right[g] n + t]   for g < n_gates,
+ *   out[g n + t] = 0 for n_gates <= g < 2^log_out.   in_dev: 2^log_in n Fr, out_dev: 2^log_out n Fr (log_out + log2 n <= 28 too);
+ * they must not overlap.  One launch.  ZKP_ERR_BAD_ARG, before anything runs: a NULL or misaligned pointer, n not a power of two,
+ * a size above these limits, out_dev over in_dev.  ZKP_ERR_BAD_HANDLE: a layer of another device.  Returns when out_dev is written. */
+int32_t zkp_fr_gkr_eval_layer_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, const uint64_t* in_dev,
+                                        uint64_t* out_dev, size_t n);
+/* One round of sum-check #1 of ZkSumcheckProof::prover (hyrax/src/zk_sumcheck_proof.rs:98-220), the one over the copy variables.
+ * The reference keeps one table of n elements per gate (temp_vec, :83-95); it is rank one, temp_vec[g][t] = w[g] eq[t] with
+ * w[g] = u0 eq(ql)[g] + u1 eq(qr)[g] and eq = eq(q'), and combine_with_r (hyrax/src/evaluate.rs:101-109) keeps it so: the call takes
+ * the n-element eq table and the weight vector instead.
+ *   v_dev:  2^log_in rows of stride n, the layer below over all copies (circuit_evals, hyrax_proof.rs:95-107); len live per row
+ *   eq_dev: n Fr, len live;   w_dev: 2^log_out Fr, of which the first n_gates are read;   len <= n, both powers of two
+ * bind_host != NULL (one Fr, Montgomery, < r, host memory): first every one of the 2^log_in rows, referenced by a gate or not, and
+ * eq become t[j] + x (t[j + len/2] - t[j]) over [0, len/2), in place (:191-203); [len/2, len) is untouched; then len /= 2.
+ * evals_out_host != NULL: three Fr (Montgomery), g(0), g(2), g(3) of
+ *   g(X) = sum_{j < len/2} eq_X[j] sum_g w[g] op_g(L_X[j], R_X[j]),   every table at lo + X (hi - lo)   (:103-156);
+ * g(1) is claim - g(0).  finals_dev != NULL (2^log_in Fr, device memory): allowed only when the length after the bind is 1;
+ * finals[i] = V[i n], the v_vec of :222-224.  A proof of v rounds is v + 1 calls, as for zkp_fr_sumcheck_round_dev: round 0
+ * without bind_host, the closing call without evals_out_host.
+ * ZKP_ERR_BAD_ARG, before anything runs or is written: a NULL v_dev / eq_dev / w_dev, a misaligned pointer, n or len not a power of
+ * two, len > n, log_in + log2 n > 28, len < 2 with bind_host, a length below 2 at evaluation time, both bind_host and
+ * evals_out_host NULL, *bind_host >= r, finals_dev with a resulting length other than 1, v / eq / finals overlapping each other
+ * or w, more than 2^20 workgroups (ceil(columns / 256) * ceil(n_gates / 32), columns = half the length at evaluation time).
+ * ZKP_ERR_BAD_HANDLE: a layer of another device.
+ * The evaluation walks the gates grouped by their left node in chunks of 32 entries, one workgroup per 256 columns and chunk:
+ * two field products per gate and three more per node that has a mul gate, no atomics, no hand-off between workgroups.  Three launches for a call
+ * that binds and evaluates, two for round 0, one for the closing call.  Bit-exact results.  Returns after the evaluations are on
+ * the host. */
+int32_t zkp_fr_gkr_dp_round_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, uint64_t* v_dev, uint64_t* eq_dev,
+                                const uint64_t* w_dev, size_t n, size_t len, const uint64_t* bind_host, uint64_t* evals_out_host,
+                                uint64_t* finals_dev);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
