@@ -198,7 +198,7 @@ int32_t zkp_ctx_create_ex(zkp_ctx** out, int device_id, const zkp_ctx_config* us
       ZKP_HIP(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming));
       ZKP_HIP(hipEventCreateWithFlags(&L.ev_a, hipEventDisableTiming));
       ZKP_HIP(hipEventCreateWithFlags(&L.ev_b1, hipEventDisableTiming));
-      ZKP_HIP(hipHostMalloc(reinterpret_cast<void**>(&L.host_proof), 1100));
+      ZKP_HIP(hipHostMalloc(reinterpret_cast<void**>(&L.host_proof), (size_t)zkp_lane::MAX_FUSE * zkp_lane::HOST_PROOF_WORDS * 4));
       for (int i = 0; i < zkp_lane::N_WS; i++) {
         ZKP_HIP(hipEventCreateWithFlags(&L.ws[i].done, hipEventDisableTiming));
         ZKP_HIP(hipEventCreateWithFlags(&L.ws[i].sorted, hipEventDisableTiming));

@@ -121,7 +121,10 @@ struct zkp_lane {
   zkp::DevBuf ntt_scratch;
   hipEvent_t ev_fork = nullptr, ev_a = nullptr, ev_b1 = nullptr;
   // pinned host landing zone of the async proof read-back
-  uint32_t* host_proof = nullptr;                               // 256 words proof + 4 words flags; host tail: A | B | C as XYZZ
+  static constexpr int MAX_FUSE = 2;                            // proofs of one fused group (groth16.hip ZKP_PROOF_FUSE) at most
+  static constexpr int HOST_PROOF_WORDS = 275;                  // landing zone of one proof; host_proof holds MAX_FUSE of them
+  uint32_t* host_proof = nullptr;                               // per proof: 256 words proof + 4 words flags; host tail: A | B | C as XYZZ
+  int group = 1;                                                // proofs of the pending fused group (prove_finish)
   bool host_tail = false;                                       // how the pending proof's points came back (prove_finish)
   bool busy = false;
 };

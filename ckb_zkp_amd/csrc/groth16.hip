@@ -69,13 +69,14 @@ struct zkp_groth16_pk {
     DevBuf proof;    // [r, s] + device proof + flags
     // hipGraph of one proof on this lane (ZKP_GRAPH=1): state 0 = never run, 1 = ran eagerly once (scratch allocated,
     // signature recorded), 2 = captured.  `sig` = every device pointer the captured launches embed.
-    bool warmed = false;   // a proof has run on this lane with this key: every scratch buffer has its size
+    int warmed = 0;        // > 0: a group of that many fused proofs (1 = a single proof) has run on this lane with this key: every scratch buffer has its size
     int graph_state = 0;
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph = nullptr;
     std::vector<const void*> sig;
   } lane[zkp_ctx::N_LANES];
   DevBuf consts;     // zinv etc.
+  uint64_t fused_groups = 0;   // fused proof groups the batches of this key have run, warm-up groups left out (zkp_groth16_pk_info)
 };
 
 namespace zkp {
@@ -151,8 +152,10 @@ __global__ void qap_consts_kernel(uint32_t* consts, int log_n) {
 
 // S tail: [1, r, s, -r*s]
 template <class P>
-__global__ void scalar_tail_kernel(uint32_t* tail, const uint32_t* rs) {
-  if (threadIdx.x || blockIdx.x) return;
+__global__ void scalar_tail_kernel(uint32_t* tail, const uint32_t* rs, size_t tail_step) {
+  if (threadIdx.x) return;
+  tail += (size_t)blockIdx.x * tail_step;                  // one workgroup per proof of a fused group: tails tail_step, [r, s] 16 words apart
+  rs += (size_t)blockIdx.x * 16;
   using F = Fp<P>;
   F r = F::load(rs), s = F::load(rs + 8);
   F::one().store(tail);
@@ -703,7 +706,7 @@ void groth16_pk_info(zkp_ctx* ctx, zkp_groth16_pk* pk, uint64_t info[8]) {
   info[3] = a[1];
   info[4] = a[3];
   info[5] = b[0];
-  info[6] = (pk->share_b_sort ? 1 : 0) | (pk->share_al_sort ? 2 : 0) | (pk->share_l1 ? 4 : 0);
+  info[6] = (pk->share_b_sort ? 1 : 0) | (pk->share_al_sort ? 2 : 0) | (pk->share_l1 ? 4 : 0) | (pk->fused_groups << 32);
   info[7] = (pk->h_lagrange ? 1 : 0) | (pk->c_folded ? 2 : 0) | (pk->chain_lh ? 4 : 0);       // key form (slots L / H)
 }
 
@@ -711,9 +714,10 @@ void groth16_pk_info(zkp_ctx* ctx, zkp_groth16_pk* pk, uint64_t info[8]) {
 // coeffs: h in coefficient form wanted (zkp_groth16_witness_map; the prover of a coefficient-form key); false with an evaluation-form
 // key: the pointwise values v on the coset, the scalars of its H MSM
 template <class P>
-static uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, bool coeffs = true) {
+static uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, bool coeffs = true, int g = 0, int G = 1) {
+  // g, G: proof g of a fused group of G (prove_enqueue_part) works in the g-th of G abc regions of the lane
   const uint32_t N = (uint32_t)pk->N;
-  uint32_t* a = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8);
+  uint32_t* a = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8 * (size_t)G) + (size_t)g * 3 * pk->N * 8;
   uint32_t* b = a + pk->N * 8;
   uint32_t* c = b + pk->N * 8;
   uint32_t* bufs[3] = {a, b, c};
@@ -770,9 +774,16 @@ void groth16_witness_map(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, ui
 // Enqueue one proof on the current lane (ctx->cur): everything is asynchronous up to and including the read-back of
 // the 3 proof points into the lane's pinned host buffer; prove_finish() synchronises the lane and hands them out.
 // part: 1 = copy the inputs (z, r, s) into the lane's buffers, 2 = everything else (the part a hipGraph captures), 3 = both
+// G > 1: a FUSED GROUP of G proofs over the same key in the kernel chain of one (zg[g], r + 4 g, s + 4 g; z is unused).  The
+// inputs lie in group-wide buffers (S: G vectors of nz + 4 scalars; [r, s] pairs 16 words apart), one scalar_tail launch covers
+// the group, every MSM runs as ONE MSM over G scalar vectors (msm.hip `sets`: window tables, sort passes, task schedule, accumulate
+// and reduction launches shared), the results fill G x 6 slots and every assembly kernel runs one workgroup per proof.  The
+// witness map runs once per proof: the group's a and b vectors through one batched transform per kind (ntt_run_batch) measured
+// the same (profiles/proof_fusion_bench.txt).  Only with the default stream plan of a pipelined batch.
 template <class FrP>
 static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
-                               const uint64_t* s, int part, char* partial_out = nullptr, bool latency_plan = false) {
+                               const uint64_t* s, int part, char* partial_out = nullptr, bool latency_plan = false, int G = 1,
+                               const uint64_t* const* zg = nullptr) {
   // partial_out != nullptr (base-sharded key): no assembly; the 5 XYZZ sums of this rank's slices (A | B1 | B2 | H | L,
   // G2-sized slots) are left at partial_out (device) for the all-gather
   ZKP_REQUIRE((pk->shard_world > 0) == (partial_out != nullptr), ZKP_ERR_BAD_ARG);
@@ -801,22 +812,26 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     ZKP_HIP(hipEventElapsedTime(dst, e0, e1));
   };
   if (prof) ZKP_HIP(hipEventRecord(eT0, st));
-  uint32_t* S = PL.S.as<uint32_t>((pk->nz + 4) * 8);
-  uint32_t* rs = PL.proof.as<uint32_t>(1024);         // [r, s] then proof words then flags
-  uint32_t* proof_dev = rs + 16;
-  uint32_t* flags_dev = proof_dev + 256;
+  ZKP_REQUIRE(G >= 1 && G <= zkp_lane::MAX_FUSE && (G == 1 || (zg && part == 3 && !partial_out && !prof)), ZKP_ERR_BAD_ARG);
+  const size_t s_stride = pk->nz + 4;                 // scalars between the S vectors of two proofs of a group
+  uint32_t* S = PL.S.as<uint32_t>(s_stride * 8 * G);
+  uint32_t* rs = PL.proof.as<uint32_t>((size_t)1024 * G);   // G x [r, s], then G x ASM_OUT_STEP proof words, then G x 4 flags
+  uint32_t* proof_dev = rs + 16 * G;
+  uint32_t* flags_dev = proof_dev + ASM_OUT_STEP * G;
   if (part & 1) {
-    ZKP_HIP(hipMemcpyAsync(S, z, pk->nz * 32, z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
-    ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
+    for (int g = 0; g < G; g++) {
+      ZKP_HIP(hipMemcpyAsync(S + g * s_stride * 8, G > 1 ? zg[g] : z, pk->nz * 32, z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+      ZKP_HIP(hipMemcpyAsync(rs + 16 * g, r + 4 * g, 32, hipMemcpyHostToDevice, st));
+      ZKP_HIP(hipMemcpyAsync(rs + 16 * g + 8, s + 4 * g, 32, hipMemcpyHostToDevice, st));
+    }
   }
   if (!(part & 2)) return;
-  hipLaunchKernelGGL(scalar_tail_kernel<FrP>, dim3(1), dim3(64), 0, st, S + pk->nz * 8, rs);
+  hipLaunchKernelGGL(scalar_tail_kernel<FrP>, dim3(G), dim3(64), 0, st, S + pk->nz * 8, rs, s_stride * 8);
 
   const MsmVtbl* v1 = msm_vtbl(pk->curve, 1);
   const MsmVtbl* v2 = msm_vtbl(pk->curve, 2);
   const size_t slot = v2->xyzz_bytes;                  // uniform slot size
-  char* res = reinterpret_cast<char*>(PL.results.get(6 * slot));
+  char* res = reinterpret_cast<char*>(PL.results.get(6 * slot * G));    // proof g: slots 6 g .. 6 g + 5
   const uint64_t* Sd = reinterpret_cast<const uint64_t*>(S);
   bool l_done_in_fan = false, g2_done_in_fan = false, chained = false;
   float acc_ms = 0.f, scan_ms = 0.f;
@@ -827,6 +842,15 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
   const zkp_tune& tune = ctx->tune;
   const bool fan = !prof && !tune.single_stream;
   uint32_t* h = nullptr;
+  size_t h_stride = 0;                               // scalars between the h vectors of two proofs of a group
+  auto witness_maps = [&]() {                        // one witness map per proof, each in its own abc region of the lane
+    h_stride = 3 * pk->N;
+    for (int g = 0; g < G; g++) {
+      uint32_t* hg = witness_map_dev<FrP>(ctx, pk, S + g * s_stride * 8, !pk->h_lagrange, g, G);
+      if (g == 0) h = hg;
+      ZKP_REQUIRE(hg == h + (size_t)g * h_stride * 8, ZKP_ERR_BAD_ARG);     // h sits at the same place in every region
+    }
+  };
   auto run = [&](int idx, uint64_t handle, const uint64_t* sc, size_t n, int w, int sort_src = -1, int l1_src = -1) {
     float ms = 0.f, ms_sc = 0.f;
     uint64_t e = 0;
@@ -837,7 +861,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     ctx->dbg_skip_k8 = ((tune.debug_skip_k8_mask >> idx) & 1) && ctx->batch_mode;
 #endif
     msm_run(ctx, handle, 0, sc, n, true, nullptr, res + idx * slot, prof ? &ms : nullptr, &e, fan ? w : 0,
-            fan ? sort_src : -1, prof ? &ms_sc : nullptr, fan ? l1_src : -1);
+            fan ? sort_src : -1, prof ? &ms_sc : nullptr, fan ? l1_src : -1, G, idx == 3 ? h_stride : s_stride, 6 * slot);
     ctx->dbg_skip_k8 = false;
     toc(&tm.ms_msm[idx]);
     acc_ms += ms;
@@ -861,7 +885,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     // them, as in round 1).  Making the other MSMs' accumulate kernels wait for it — a kernel timeline shows machine-filling
     // accumulates from three streams leaving its kernels few wave slots for milliseconds — was measured too: 10.3 ms, not kept.
     if (tune.wm_first) {
-      h = witness_map_dev<FrP>(ctx, pk, S, !pk->h_lagrange);
+      witness_maps();
       ctx->mark(st, "wm");
     }
     // (Round 4, measured with ZKP_TIMELINE=1 and removed again: holding the accumulate kernels of A / B1 / B2 / L until the witness map
@@ -873,6 +897,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     const bool l_own = tune.l_own_stream;
     (void)latency_plan;
     const bool lat = tune.latency_plan >= 0 ? tune.latency_plan != 0 : true;
+    ZKP_REQUIRE(G == 1 || lat, ZKP_ERR_BAD_ARG);
     if (lat) {
       // Stream plan (round 2; default for single proofs AND the pipelined batch — measured 113.6 vs 111.2 proofs/s and 11.0 vs
       // 11.9 ms single-proof latency against the round-1 plan below, which ZKP_LATENCY_PLAN=0 restores):
@@ -886,7 +911,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
       if (b_l1) run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 2, -1, l1);
       // proof.b needs B2 only: its into_affine runs on B2's stream as soon as the MSM is done instead of in the tail of the proof
       if (!partial_out && tune.g2_early && !host_tail) {
-        v2->assemble_g2(ctx->cur->ws[2].stream, res, slot, proof_dev, flags_dev, 2 * v1->fN);
+        v2->assemble_g2(ctx->cur->ws[2].stream, res, slot, proof_dev, flags_dev, 2 * v1->fN, G);
         g2_done_in_fan = true;
       }
       run(1, pk->hB1, Sd + 4 * pk->q_lo[1], pk->q_n[1], 3, pk->share_b_sort ? 2 : -1);
@@ -894,7 +919,7 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
       run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 1, pk->share_al_sort ? 1 : -1, l1);   // A's sort / level-1 pass, still in this workspace
       if (!partial_out) {
         ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[3].stream, ctx->cur->ev_a, 0));
-        v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev);
+        v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, G);
         ctx->tl_tag.clear();
         ctx->mark(ctx->cur->ws[3].stream, "part1");
       }
@@ -911,13 +936,14 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     // A and B1 exist so they hide under the remaining MSMs
     if (!partial_out) {
       ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[3].stream, ctx->cur->ev_b1, 0));
-      v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev);
+      v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, 1);
     }
     }
     l_done_in_fan = lat || l_own;
   }
+  ZKP_REQUIRE(G == 1 || fan, ZKP_ERR_BAD_ARG);
   tic();
-  if (!h) h = witness_map_dev<FrP>(ctx, pk, S, !pk->h_lagrange);
+  if (!h) witness_maps();
   toc(&tm.ms_witness_map);
   if (!fan) {
     run(0, pk->hA, Sd + 4 * pk->q_lo[0], pk->q_n[0], 0);
@@ -952,27 +978,31 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
 
   tic();
   // proof layout (32-bit words): A = 2*fN1 | B = 2*fN2 | C = 2*fN1
-  if (!fan) v1->assemble_g1_part1(st, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev);
-  v1->assemble_g1_part2(st, res, slot, host_tail ? nullptr : proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN);
-  if (!g2_done_in_fan && !host_tail) v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN);
+  if (!fan) v1->assemble_g1_part1(st, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, 1);
+  v1->assemble_g1_part2(st, res, slot, host_tail ? nullptr : proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN, G);
+  if (!g2_done_in_fan && !host_tail) v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN, G);
   ZKP_HIP(hipGetLastError());
   toc(&tm.ms_assemble);
   const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
-  if (host_tail) {
-    // the three proof points go back as XYZZ (A = slot 0, B = slot 2, C = slot 5); prove_finish makes them affine on the host
-    // with one inversion (host_field.hpp) — three single-lane Fermat chains (0.25-0.32 ms each) leave the tail of the proof
-    uint32_t* hp = ctx->cur->host_proof;
-    ZKP_HIP(hipMemcpyAsync(hp, res, 16 * (size_t)v1->fN, hipMemcpyDeviceToHost, st));
-    ZKP_HIP(hipMemcpyAsync(hp + 4 * v1->fN, res + 2 * slot, 16 * (size_t)v2->fN, hipMemcpyDeviceToHost, st));
-    ZKP_HIP(hipMemcpyAsync(hp + 4 * v1->fN + 4 * v2->fN, res + 5 * slot, 16 * (size_t)v1->fN, hipMemcpyDeviceToHost, st));
-  } else {
-    ZKP_HIP(hipMemcpyAsync(ctx->cur->host_proof, proof_dev, proof_words * 4, hipMemcpyDeviceToHost, st));
-    ZKP_HIP(hipMemcpyAsync(ctx->cur->host_proof + 256, flags_dev, 12, hipMemcpyDeviceToHost, st));
+  for (int g = 0; g < G; g++) {                              // proof g lands HOST_PROOF_WORDS words behind proof g - 1
+    uint32_t* hp = ctx->cur->host_proof + (size_t)g * zkp_lane::HOST_PROOF_WORDS;
+    const char* rg = res + (size_t)g * 6 * slot;
+    if (host_tail) {
+      // the three proof points go back as XYZZ (A = slot 0, B = slot 2, C = slot 5); prove_finish makes them affine on the host
+      // with one inversion (host_field.hpp) — three single-lane Fermat chains (0.25-0.32 ms each) leave the tail of the proof
+      ZKP_HIP(hipMemcpyAsync(hp, rg, 16 * (size_t)v1->fN, hipMemcpyDeviceToHost, st));
+      ZKP_HIP(hipMemcpyAsync(hp + 4 * v1->fN, rg + 2 * slot, 16 * (size_t)v2->fN, hipMemcpyDeviceToHost, st));
+      ZKP_HIP(hipMemcpyAsync(hp + 4 * v1->fN + 4 * v2->fN, rg + 5 * slot, 16 * (size_t)v1->fN, hipMemcpyDeviceToHost, st));
+    } else {
+      ZKP_HIP(hipMemcpyAsync(hp, proof_dev + (size_t)g * ASM_OUT_STEP, proof_words * 4, hipMemcpyDeviceToHost, st));
+      ZKP_HIP(hipMemcpyAsync(hp + 256, flags_dev + 4 * g, 12, hipMemcpyDeviceToHost, st));
+    }
   }
   ctx->tl_tag.clear();
   ctx->mark(st, "copied");
   ctx->cur->host_tail = host_tail;
   ctx->cur->busy = true;
+  ctx->cur->group = G;
   if (prof) {
     ZKP_HIP(hipEventRecord(eT1, st));
     ZKP_HIP(hipStreamSynchronize(st));
@@ -1066,16 +1096,20 @@ static void prove_finish(zkp_ctx* ctx, zkp_groth16_pk* pk, uint64_t* proof_out, 
     ctx->tl.clear();
     fprintf(stderr, "%s\n", line.c_str());
   }
-  if (ctx->cur->host_tail) {
-    const hostf::HostField Fq = hostf::fq_field(pk->curve);
-    const uint32_t* hp = ctx->cur->host_proof;
-    hostf::groth16_points_into_affine(Fq, hp, hp + 4 * v1->fN, hp + 4 * v1->fN + 4 * v2->fN,
-                                      reinterpret_cast<uint32_t*>(proof_out), inf_out);
-  } else {
-    memcpy(proof_out, ctx->cur->host_proof, proof_words * 4);
-    for (int i = 0; i < 3; i++) inf_out[i] = (uint8_t)ctx->cur->host_proof[256 + i];
+  // a fused group hands out its proofs one behind the other: they are consecutive proofs of the batch
+  for (int g = 0; g < ctx->cur->group; g++) {
+    const uint32_t* hp = ctx->cur->host_proof + (size_t)g * zkp_lane::HOST_PROOF_WORDS;
+    uint32_t* po = reinterpret_cast<uint32_t*>(proof_out) + (size_t)g * proof_words;
+    if (ctx->cur->host_tail) {
+      const hostf::HostField Fq = hostf::fq_field(pk->curve);
+      hostf::groth16_points_into_affine(Fq, hp, hp + 4 * v1->fN, hp + 4 * v1->fN + 4 * v2->fN, po, inf_out + 3 * g);
+    } else {
+      memcpy(po, hp, proof_words * 4);
+      for (int i = 0; i < 3; i++) inf_out[3 * g + i] = (uint8_t)hp[256 + i];
+    }
   }
   ctx->cur->busy = false;
+  ctx->cur->group = 1;
 }
 
 void groth16_assemble(zkp_ctx* ctx, int curve, const uint64_t* sums, const uint64_t* r, const uint64_t* s,
@@ -1097,9 +1131,9 @@ void groth16_assemble(zkp_ctx* ctx, int curve, const uint64_t* sums, const uint6
   ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
   const size_t off[5] = {0, j1, 2 * j1, 2 * j1 + j2, 3 * j1 + j2};
   for (int i = 0; i < 5; i++) (i == 2 ? v2 : v1)->from_jacobian(st, jac + off[i], res + i * slot);
-  v1->assemble_g1_part1(st, res, slot, rs, proof_dev, flags_dev);
-  v1->assemble_g1_part2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN);
-  v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN);
+  v1->assemble_g1_part1(st, res, slot, rs, proof_dev, flags_dev, 1);
+  v1->assemble_g1_part2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN, 1);
+  v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN, 1);
   ZKP_HIP(hipGetLastError());
   const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
   uint32_t flags_host[4] = {0, 0, 0, 0};
@@ -1141,9 +1175,9 @@ void groth16_fold_assemble(zkp_ctx* ctx, int curve, const void* gathered_dev, in
   ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
   v1->fold_slots(st, (const char*)gathered_dev, 5 * slot, world, slot, 0x1b, res);     // A, B1, H, L
   v2->fold_slots(st, (const char*)gathered_dev, 5 * slot, world, slot, 0x04, res);     // B2
-  v1->assemble_g1_part1(st, res, slot, rs, proof_dev, flags_dev);
-  v1->assemble_g1_part2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN);
-  v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN);
+  v1->assemble_g1_part1(st, res, slot, rs, proof_dev, flags_dev, 1);
+  v1->assemble_g1_part2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN, 1);
+  v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN, 1);
   ZKP_HIP(hipGetLastError());
   const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
   uint32_t flags_host[4] = {0, 0, 0, 0};
@@ -1165,8 +1199,19 @@ void groth16_prove(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_o
   prove_finish(ctx, pk, proof_out, inf_out);
 }
 
-// n proofs, software-pipelined over the two lanes: proof i+1 is enqueued before proof i is awaited, so the
-// latency-bound tails (bucket reduction, assembly) of one proof overlap the throughput-bound kernels of the next.
+// n proofs, software-pipelined over the lanes (8, or 4 above 2^22): group i+1 is enqueued before group i is awaited, so the
+// latency-bound tails (bucket reduction, assembly) of one overlap the throughput-bound kernels of the next.
+//
+// Fused groups.  ZKP_PROOF_FUSE (compile time, 1 or 2) consecutive proofs share ONE kernel chain (prove_enqueue_part G > 1): the
+// ~155 latency-bound launches of a proof (scans, task scheduling, pyramid tops, final sums, assembly) each use a sliver of the device
+// but hold a hardware queue while they run, and they last about as long for two proofs as for one.  A group runs on one lane with
+// that lane's four streams and the unchanged stream plan.  An odd remainder, profiling runs, ZKP_GRAPH=1, ZKP_SINGLE_STREAM=1,
+// ZKP_LATENCY_PLAN=0, window-group keys and domains above 2^22 take the one-proof path.  -DZKP_PROOF_FUSE=1 is the code path
+// without groups (A/B builds).
+#ifndef ZKP_PROOF_FUSE
+#define ZKP_PROOF_FUSE 2
+#endif
+static_assert(ZKP_PROOF_FUSE == 1 || ZKP_PROOF_FUSE == 2, "group size: 1 or 2 (= zkp_lane::MAX_FUSE); larger groups are not tested");
 void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint64_t* const* z_dev, const uint64_t* r,
                          const uint64_t* s, uint64_t* proofs_out, uint8_t* inf_out, bool z_on_device) {
   const MsmVtbl* v1 = msm_vtbl(pk->curve, 1);
@@ -1193,21 +1238,39 @@ void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint6
     ~BatchMode() { c->batch_mode = false; }
   } batch_mode{ctx};
   ctx->batch_mode = n > 1 && !prof;
+  // proofs per kernel chain, when everything a fused group needs holds
+  int fuse = 1;
+  if (ZKP_PROOF_FUSE > 1 && ctx->batch_mode && !ctx->tune.graph && !ctx->tune.single_stream && ctx->tune.latency_plan != 0 &&
+      pk->log_n <= 22) {
+    fuse = ZKP_PROOF_FUSE;
+    for (uint64_t hq : {pk->hA, pk->hB1, pk->hB2, pk->hH, pk->hL})
+      if (!msm_sets_ok(ctx, hq, fuse)) fuse = 1;
+  }
+  auto enqueue = [&](size_t i, int G) {                      // proofs i .. i + G - 1 on the current lane
+    if (pk->curve == ZKP_BN254) {
+      if (G > 1) prove_enqueue_part<Bn254Fr>(ctx, pk, nullptr, z_on_device, r + 4 * i, s + 4 * i, 3, nullptr, false, G, z_dev + i);
+      else prove_enqueue<Bn254Fr>(ctx, pk, z_dev[i], z_on_device, r + 4 * i, s + 4 * i);
+    } else {
+      if (G > 1) prove_enqueue_part<Bls381Fr>(ctx, pk, nullptr, z_on_device, r + 4 * i, s + 4 * i, 3, nullptr, false, G, z_dev + i);
+      else prove_enqueue<Bls381Fr>(ctx, pk, z_dev[i], z_on_device, r + 4 * i, s + 4 * i);
+    }
+  };
   try {
     // First pipelined batch of this key: a lane's scratch (bucket arrays, sort buffers, NTT scratch: GiBs at 2^22) is allocated
     // when a proof first runs on it, and hipMalloc synchronises the device.  A batch shorter than the lane count would leave
     // that to a later call's steady state (measured: a 12-proof batch after a 4-proof one ran at 11 instead of 19 proofs/s at
     // 2^22 BLS12-381), so the lanes this key has never used run the first proof once, results discarded.
+    // A fused group needs larger scratch than one proof (and covers it), so a batch that will run groups warms with a group.
     if (ctx->batch_mode) {
-      std::vector<uint64_t> scratch_proof(pw64 + 8);
-      uint8_t scratch_inf[4];
+      const int warm = (size_t)fuse <= n ? fuse : 1;
+      std::vector<uint64_t> scratch_proof(pw64 * warm + 8);
+      uint8_t scratch_inf[3 * zkp_lane::MAX_FUSE + 1];
       bool any = false;
       for (int l = 0; l < nl; l++) {
-        if (pk->lane[l].warmed) continue;
+        if (pk->lane[l].warmed >= warm) continue;
         select(l);
-        if (pk->curve == ZKP_BN254) prove_enqueue<Bn254Fr>(ctx, pk, z_dev[0], z_on_device, r, s);
-        else prove_enqueue<Bls381Fr>(ctx, pk, z_dev[0], z_on_device, r, s);
-        pk->lane[l].warmed = true;
+        enqueue(0, warm);
+        pk->lane[l].warmed = warm;
         any = true;
       }
       if (any)
@@ -1216,13 +1279,16 @@ void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint6
           if (ctx->cur->busy) prove_finish(ctx, pk, scratch_proof.data(), scratch_inf);
         }
     }
-    for (size_t i = 0; i < n; i++) {
-      const int l = prof ? 0 : (int)(i % nl);
+    size_t k = 0;                                            // groups (or single proofs) enqueued so far
+    for (size_t i = 0; i < n; k++) {
+      const int G = n - i >= (size_t)fuse ? fuse : 1;          // the remainder goes one proof at a time
+      const int l = prof ? 0 : (int)(k % nl);
       select(l);
       if (ctx->cur->busy) prove_finish(ctx, pk, proofs_out + pending[l] * pw64, inf_out + pending[l] * 3);
-      if (pk->curve == ZKP_BN254) prove_enqueue<Bn254Fr>(ctx, pk, z_dev[i], z_on_device, r + 4 * i, s + 4 * i);
-      else prove_enqueue<Bls381Fr>(ctx, pk, z_dev[i], z_on_device, r + 4 * i, s + 4 * i);
+      enqueue(i, G);
+      if (G > 1) pk->fused_groups++;
       pending[l] = i;
+      i += G;
     }
     for (int l = 0; l < zkp_ctx::N_LANES; l++) {
       select(l);
@@ -1543,7 +1609,7 @@ void prove_multi_t(zkp_ctx* root, zkp_groth16_pk_multi* M, const uint64_t* const
     ZKP_HIP(hipMemcpyAsync(S[k], zk, pk->nz * 32, z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
     ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(scalar_tail_kernel<FrP>, dim3(1), dim3(64), 0, st, S[k] + pk->nz * 8, rs);
+    hipLaunchKernelGGL(scalar_tail_kernel<FrP>, dim3(1), dim3(64), 0, st, S[k] + pk->nz * 8, rs, (size_t)0);
     ZKP_HIP(hipEventRecord(ctx->cur->ev_fork, st));
     for (int w = 1; w < zkp_ctx::N_WS; w++) ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[w].stream, ctx->cur->ev_fork, 0));
     if (!split) h[k] = witness_map_dev<FrP>(ctx, pk, S[k], !pk->h_lagrange);

@@ -55,7 +55,13 @@ int bases_group(zkp_ctx* ctx, uint64_t handle);
 // runs on workspace `ws` (its stream + scratch); does not synchronise unless out_xyz_host != nullptr
 void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scalars_dev, size_t n, bool montgomery,
              uint64_t* out_xyz_host, void* out_dev_xyzz = nullptr, float* ms_accumulate = nullptr,
-             uint64_t* n_entries = nullptr, int ws = 0, int sort_src = -1, float* ms_scan = nullptr, int l1_src = -1);
+             uint64_t* n_entries = nullptr, int ws = 0, int sort_src = -1, float* ms_scan = nullptr, int l1_src = -1,
+             int sets = 1, size_t set_stride = 0, size_t out_stride = 0);
+// sets == 2: ONE kernel chain computes `sets` MSMs over the same resident bases — scalar vector g lies set_stride scalars
+// behind vector g - 1 and its XYZZ result out_stride bytes behind result g - 1 (out_dev_xyzz only, no host read-back).  Sort
+// sharing (sort_src, l1_src) and bucket chaining work as for one MSM when both partners use the same `sets`.  msm_sets_ok: whether
+// this base vector and the context's switches allow it (fixed-base plan, fused pyramid top).
+bool msm_sets_ok(zkp_ctx* ctx, uint64_t handle, int sets);
 // bench_kern.hip: sustained rate (1e9 products/s) of the library's Montgomery multipliers; field 0 = Fr, 1 = Fq
 double bench_mulmod(zkp_ctx* ctx, int curve, int field, bool unsaturated);
 // bench_kern.hip: GB/s (read + written) of a streaming device-to-device copy kernel over two `bytes`-byte buffers

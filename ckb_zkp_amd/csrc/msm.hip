@@ -36,6 +36,7 @@
 #include "field_dev.hpp"
 #include "internal.hpp"
 #include "msm_digits.hpp"
+#include "msm_pyramid.hpp"
 #include "msm_small.hpp"
 #include "msm_vtbl.hpp"
 
@@ -402,9 +403,13 @@ __global__ __launch_bounds__(NT) void sort_hist_kernel(const uint32_t* __restric
                                                         const uint8_t* __restrict__ inf, int montgomery, int c, int W, int wide,
                                                         uint32_t nb, int L, uint32_t nbins1,
                                                         uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t tile,
-                                                        int lgk) {
+                                                        int lgk, size_t set_words) {
   ZKP_SORT_PRIO();
   const uint32_t gmask = (1u << lgk) - 1;                          // window w -> bucket set w & gmask, table copy w >> lgk
+  // blockIdx.y = scalar vector g of a fused MSM (msm_run_entry `sets`): its scalars lie set_words words further on and its
+  // nbins1 level-1 bins follow those of vector g - 1, so the bucket ids of vector g carry g as their highest bits
+  scalars += (size_t)blockIdx.y * set_words;
+  hist += (size_t)blockIdx.y * nbins1 * nblocks;
   __shared__ uint32_t cnt[(1 << SORT_H1_MAX) + 1];
   for (uint32_t i = threadIdx.x; i <= nbins1; i += NT) cnt[i] = 0;
   __syncthreads();
@@ -429,9 +434,11 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
                                                            int L, uint32_t nbins1, const uint32_t* __restrict__ offs,
                                                            uint32_t nblocks, uint32_t tile,
                                                            uint64_t* __restrict__ kv, int lgk,
-                                                           const uint8_t* __restrict__ group_flags) {   // (low key << 32) | val
+                                                           const uint8_t* __restrict__ group_flags, size_t set_words) {   // (low key << 32) | val
   ZKP_SORT_PRIO();
   const uint32_t gmask = (1u << lgk) - 1;
+  scalars += (size_t)blockIdx.y * set_words;                    // scalar vector blockIdx.y and its bins (sort_hist_kernel)
+  offs += (size_t)blockIdx.y * nbins1 * nblocks;
   __shared__ uint32_t cur[(1 << SORT_H1_MAX) + 1];
   for (uint32_t i = threadIdx.x; i < nbins1; i += 256) cur[i] = offs[(size_t)i * nblocks + blockIdx.x];
   __syncthreads();
@@ -527,9 +534,12 @@ __global__ __launch_bounds__(NT) void sort_scatter_staged_kernel(const uint32_t*
                                                                   int montgomery, size_t ntab, int c, int W, int wide, uint32_t nb,
                                                                   int L, uint32_t nbins1, const uint32_t* __restrict__ offs,
                                                                   uint32_t nblocks, uint32_t tile, uint64_t* __restrict__ kv,
-                                                                  int lgk, const uint8_t* __restrict__ group_flags, uint32_t sub) {
+                                                                  int lgk, const uint8_t* __restrict__ group_flags, uint32_t sub,
+                                                                  size_t set_words) {
   ZKP_SORT_PRIO();
   const uint32_t gmask = (1u << lgk) - 1;
+  scalars += (size_t)blockIdx.y * set_words;                    // scalar vector blockIdx.y and its bins (sort_hist_kernel)
+  offs += (size_t)blockIdx.y * nbins1 * nblocks;
   extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
   __shared__ uint32_t pre[NT];
   uint32_t* cur = sm;                                     // [nbins1] next free slot of (bin, this tile) in kv
@@ -796,10 +806,20 @@ __global__ void sched_check_kernel(const uint32_t* toff, const uint32_t* long_li
 
 static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, const uint64_t* scalars_dev, size_t n,
                           bool montgomery, uint64_t* out_xyz_host, void* out_dev_xyzz, float* ms_accumulate,
-                          uint64_t* n_entries, int ws_idx, int sort_src, float* ms_scan, int l1_src = -1);
+                          uint64_t* n_entries, int ws_idx, int sort_src, float* ms_scan, int l1_src = -1, int sets = 1,
+                          size_t set_stride = 0, size_t out_stride = 0);
+bool msm_sets_ok(zkp_ctx* ctx, uint64_t handle, int sets) {
+  auto be = get_bases(ctx, handle);
+  const zkp_tune& t = ctx->tune;
+  int lgs = 0;
+  while ((1 << lgs) < sets) lgs++;
+  // the per-set reduction exists for the fixed-base plan with the fused pyramid top (msm_run_entry); the product with W bounds E
+  return sets >= 1 && sets <= 2 && (1 << lgs) == sets && !be->var && t.pair_top && t.pair_top_fuse_seg &&
+         (t.sort_h1 <= 0 || t.sort_h1 >= lgs) && (double)be->n * be->W * sets < 2147483000.0;
+}
 void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scalars_dev, size_t n, bool montgomery,
              uint64_t* out_xyz_host, void* out_dev_xyzz, float* ms_accumulate, uint64_t* n_entries, int ws_idx,
-             int sort_src, float* ms_scan, int l1_src) {
+             int sort_src, float* ms_scan, int l1_src, int sets, size_t set_stride, size_t out_stride) {
   struct ChainReset {                // one-shot requests: never leak into a later MSM, whatever this call throws (bad handle, ...)
     zkp_ctx* c;
     ~ChainReset() {
@@ -818,10 +838,10 @@ void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scala
   const size_t chunk_pts = (size_t)std::max<long long>(0, ctx->cfg.msm_chunk);        // zkp_ctx_config.msm_chunk_points / ZKP_MSM_CHUNK
   const bool chunkable = chunk_pts >= 1024 && n >= 2 * chunk_pts && be->group == 1 && !be->var && sort_src < 0 && l1_src < 0 &&
                          !be->group_flags && !ctx->profiling && !ms_accumulate && !ms_scan && !n_entries &&
-                         !ctx->msm_defer_reduce && ctx->msm_acc_into < 0 && ctx->msm_bucket_ws < 0 && !ctx->batch_mode;
+                         !ctx->msm_defer_reduce && ctx->msm_acc_into < 0 && ctx->msm_bucket_ws < 0 && !ctx->batch_mode && sets == 1;
   if (!chunkable) {
     msm_run_entry(ctx, be.get(), offset, scalars_dev, n, montgomery, out_xyz_host, out_dev_xyzz, ms_accumulate, n_entries,
-                  ws_idx, sort_src, ms_scan, l1_src);
+                  ws_idx, sort_src, ms_scan, l1_src, sets, set_stride, out_stride);
     return;
   }
   // (per is rounded up to a multiple of 256, so the chunk count is recomputed from it: with a ZKP_MSM_CHUNK that is not a multiple
@@ -899,7 +919,18 @@ static VarPlan& var_plan(zkp_ctx* ctx, int c, int W, hipStream_t st) {
 
 static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, const uint64_t* scalars_dev, size_t n,
                           bool montgomery, uint64_t* out_xyz_host, void* out_dev_xyzz, float* ms_accumulate,
-                          uint64_t* n_entries, int ws_idx, int sort_src, float* ms_scan, int l1_src) {
+                          uint64_t* n_entries, int ws_idx, int sort_src, float* ms_scan, int l1_src, int sets, size_t set_stride,
+                          size_t out_stride) {
+  // sets > 1 (a power of two): ONE kernel chain for `sets` independent MSMs over the same bases — scalar vector g starts
+  // set_stride scalars behind vector g - 1, its XYZZ result goes out_stride bytes behind that of g - 1 and its Jacobian 3 fN words
+  // behind it in the workspace's `out`.  The proof index is one more set dimension on top of the window groups (lgk): bucket id =
+  // (g << (c - 1 + lgk)) | (set << (c - 1)) | key.  Everything from level 2 of the sort to `combine` sees sets * nb buckets; the
+  // reduction yields one result per vector.  Fixed-base plan with the fused pyramid top only (msm_sets_ok).
+  int lgs = 0;
+  while ((1 << lgs) < sets) lgs++;
+  ZKP_REQUIRE(sets == 1 || sets == 2, ZKP_ERR_BAD_ARG);        // the index arithmetic is written for 2^lgs sets; only 1 and 2 are tested
+  ZKP_REQUIRE(sets == 1 || (!be->var && !out_xyz_host && ctx->tune.pair_top && ctx->tune.pair_top_fuse_seg), ZKP_ERR_BAD_ARG);
+  const uint32_t S = (uint32_t)sets;
   const MsmVtbl* vt = be->vt;
   MsmWorkspace& ws = ctx->cur->ws[ws_idx];
   // bucket chaining (ctx.hpp): one-shot requests, consumed by this MSM
@@ -917,21 +948,22 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
   hipStream_t st = ws_idx == 0 ? ctx->cur->stream : ws.stream;
   const size_t XB = vt->bucket_bytes;                                // buckets, partial sums, pyramid levels
   const size_t jac_words = 3 * (size_t)vt->fN;
-  uint32_t* out_jac = ws.out.as<uint32_t>(64 * 4);
+  uint32_t* out_jac = ws.out.as<uint32_t>((size_t)64 * 4 * S);
   if (ms_accumulate) *ms_accumulate = 0.f;
   if (ms_scan) *ms_scan = 0.f;
   if (n_entries) *n_entries = 0;
   if (n == 0) {
-    vt->write_identity(st, (char*)out_dev_xyzz, out_jac);
+    vt->write_identity(st, (char*)out_dev_xyzz, out_jac, S, out_stride, (uint32_t)jac_words);
   } else {
     const int c = be->c, W = be->W, wide = be->wide;
     const int var = be->var ? 1 : 0;
     const int lgk = be->lgk, K = 1 << lgk;                             // bucket sets (window groups, BasesEntry::lgk)
     ZKP_REQUIRE(var == (lgk > 0), ZKP_ERR_BAD_ARG);
     const uint32_t nb_w = 1u << (c - 1);                               // buckets of one window (digit range)
-    const int kbits = (c - 1) + lgk;                                   // bits of a bucket id
-    const uint32_t nb = 1u << kbits;                                   // all buckets
-    const size_t E = n * (size_t)W;
+    const int kbits = (c - 1) + lgk + lgs;                             // bits of a bucket id
+    const uint32_t nb = 1u << kbits;                                   // all buckets (of all scalar vectors)
+    const uint32_t nb_set = nb >> lgs;                                 // buckets of one scalar vector
+    const size_t E = n * (size_t)W * S;
     ZKP_REQUIRE(E < 2147483000ull, ZKP_ERR_BAD_ARG);
     // l1_src >= 0 (and no full reuse): the level-1 pass over these scalars — digit scan, (bin, tile) counts, scatter into bins —
     // was run by workspace l1_src of this lane for a GROUP of queries (it dropped only the bases that are the identity in all of
@@ -953,8 +985,11 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     if (h1_env > 0) H1 = std::min(SORT_H1_MAX, h1_env);
     H1 = std::min(H1, kbits);
     if (kbits - H1 > SORT_L_MAX) H1 = kbits - SORT_L_MAX;
+    ZKP_REQUIRE(H1 >= lgs, ZKP_ERR_BAD_ARG);                           // a level-1 bin never straddles two scalar vectors
     const int LB = kbits - H1;                                         // low bits per level-1 bin
     const uint32_t nbins1 = 1u << H1;
+    const uint32_t nbins_set = nbins1 >> lgs;                          // level-1 bins of one scalar vector (what the level-1 kernels see)
+    const size_t set_words = set_stride * 8;
     uint32_t tile = SORT_SCALARS;
     while ((n + tile - 1) / tile > 1536) tile += 256;
     const uint32_t nblocks = (uint32_t)((n + tile - 1) / tile);
@@ -977,10 +1012,10 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     // not for > 2048 level-1 bins (the two counter arrays would leave one workgroup per CU) or very narrow windows
     uint32_t staged_sub = 0;
     size_t staged_lds = 0;
-    if (tune.sort_staged && nbins1 <= 2048 && (size_t)256 * W * 8 <= SORT_STAGE_BYTES) {
+    if (tune.sort_staged && nbins_set <= 2048 && (size_t)256 * W * 8 <= SORT_STAGE_BYTES) {
       staged_sub = (uint32_t)(SORT_STAGE_BYTES / ((size_t)W * 8)) / 256 * 256;
       staged_sub = std::min<uint32_t>(staged_sub, tile);
-      staged_lds = ((size_t)nbins1 + ((nbins1 + 3) & ~3u)) * 4 + (size_t)staged_sub * W * 8;
+      staged_lds = ((size_t)nbins_set + ((nbins_set + 3) & ~3u)) * 4 + (size_t)staged_sub * W * 8;
     }
     const bool timed_scan = ms_scan && ctx->profiling && !reuse && !l1_reuse;      // K5 "scalar scan": histogram pass + count scan + scatter pass
     if (timed_scan) ZKP_HIP(hipEventRecord(ctx->ev2, st));
@@ -992,8 +1027,8 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
         using FrP = decltype(tag);
         auto hist_l = [&](auto nt) {
           constexpr int NT = decltype(nt)::value;
-          hipLaunchKernelGGL((sort_hist_kernel<FrP, NT>), dim3(nblocks), dim3(NT), 0, st, sc, n, offset, scan_inf, mont, c, W, wide, nb_w,
-                             LB, nbins1, hist, nblocks, tile, lgk);
+          hipLaunchKernelGGL((sort_hist_kernel<FrP, NT>), dim3(nblocks, S), dim3(NT), 0, st, sc, n, offset, scan_inf, mont, c, W, wide, nb_w,
+                             LB, nbins_set, hist, nblocks, tile, lgk, set_words);
         };
         if (nt_hist >= 1024) hist_l(std::integral_constant<int, 1024>{});
         else if (nt_hist >= 512) hist_l(std::integral_constant<int, 512>{});
@@ -1002,15 +1037,16 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
         if (staged_sub) {
           auto scat_l = [&](auto nt) {
             constexpr int NT = decltype(nt)::value;
-            hipLaunchKernelGGL((sort_scatter_staged_kernel<FrP, NT>), dim3(nblocks), dim3(NT), staged_lds, st, sc, n, offset,
-                               scan_inf, mont, be->n, c, W, wide, nb_w, LB, nbins1, offs, nblocks, tile, kv, lgk, grp, staged_sub);
+            hipLaunchKernelGGL((sort_scatter_staged_kernel<FrP, NT>), dim3(nblocks, S), dim3(NT), staged_lds, st, sc, n, offset,
+                               scan_inf, mont, be->n, c, W, wide, nb_w, LB, nbins_set, offs, nblocks, tile, kv, lgk, grp, staged_sub,
+                               set_words);
           };
           if (nt_scat >= 1024) scat_l(std::integral_constant<int, 1024>{});
           else if (nt_scat >= 512) scat_l(std::integral_constant<int, 512>{});
           else scat_l(std::integral_constant<int, 256>{});
         } else {
-          hipLaunchKernelGGL(sort_scatter_kernel<FrP>, dim3(nblocks), dim3(256), 0, st, sc, n, offset, scan_inf, mont, be->n, c, W, wide,
-                             nb_w, LB, nbins1, offs, nblocks, tile, kv, lgk, grp);
+          hipLaunchKernelGGL(sort_scatter_kernel<FrP>, dim3(nblocks, S), dim3(256), 0, st, sc, n, offset, scan_inf, mont, be->n, c, W, wide,
+                             nb_w, LB, nbins_set, offs, nblocks, tile, kv, lgk, grp, set_words);
         }
       };
       if (be->curve == ZKP_BN254) level1(Bn254Fr{});
@@ -1139,7 +1175,7 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
       bws.chain_nb = nb;
       bws.chain_xb = XB;
       ZKP_HIP(hipEventRecord(bws.acc_done, st));
-      vt->write_identity(st, (char*)out_dev_xyzz, out_jac);
+      vt->write_identity(st, (char*)out_dev_xyzz, out_jac, S, out_stride, (uint32_t)jac_words);
       ZKP_HIP(hipGetLastError());
       ZKP_REQUIRE(!out_xyz_host, ZKP_ERR_BAD_ARG);
       return;
@@ -1153,46 +1189,44 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     plan.L = L;
     const uint32_t chunk = ctx->batch_mode ? SEG_CHUNK_BATCH : SEG_CHUNK;
     plan.chunk = chunk;
-    uint32_t lvl_off = 0, cnt = nb, blocks = 0;
+    // Where the levels live: msm_pyramid.hpp (with S scalar vectors the sets lie side by side up to the level the fused top starts
+    // from; the top of set g then writes into a region of its own).  blocks, first_block, count: per set.
     // Round 6: the one-workgroup top of the pyramid and the segmented sums of the levels below it run in ONE launch (msm_group.hip
     // pair_top_segsum_kernel); the second stage then sums the partials of the low levels and, directly from the pyramid, the odd
     // entries of the top's levels (<= PAIR_TOP_MAX / 2 = one block each).  ZKP_PAIR_TOP_FUSE_SEG=0: pair_top, then both stages (rounds 3-5).
-    const bool fuse_seg = tune.pair_top_fuse_seg;
-    int l_top = -1;                                // first level the fused top produces the successor of
-    char* top_base = nullptr;
-    uint32_t top_cnt = 0;
+    // (ZKP_PAIR_TOP_MAX is rounded down to a power of two: the fused top starts at the level whose size EQUALS top_max)
+    const bool top_fused = tune.pair_top;
+    const uint32_t top_max = (uint32_t)tune.pair_top_max;
+    const PyramidLevels lv = pyramid_levels(nb_set, S, L, top_fused && tune.pair_top_fuse_seg, top_max, chunk);
+    ZKP_REQUIRE(lv.end <= 2 * nb, ZKP_ERR_BAD_ARG);       // the bucket buffer holds 2 nb + 1 points
+    const int l_top = lv.l_top;                      // first level the fused top produces the successor of
+    char* const top_base = l_top >= 0 ? buckets + (size_t)lv.off[l_top] * XB : nullptr;
+    const uint32_t top_cnt = lv.top_cnt;
+    uint32_t blocks = 0;
     for (int l = 0; l < L; l++) {
-      uint32_t next_off = lvl_off + cnt;
-      // (ZKP_PAIR_TOP_MAX is rounded down to a power of two: the fused top starts at the level whose size EQUALS top_max)
-      const bool top_fused = tune.pair_top;
-      const uint32_t top_max = (uint32_t)tune.pair_top_max;
-      if (!top_fused || cnt > top_max) vt->pair(st, buckets + (size_t)lvl_off * XB, buckets + (size_t)next_off * XB, cnt / 2);
-      else if (cnt == top_max || l == 0) {         // this level and all above it
-        if (fuse_seg && cnt / 2 <= chunk) {
-          l_top = l;
-          top_base = buckets + (size_t)lvl_off * XB;
-          top_cnt = cnt;
-        } else {
-          vt->pair_top(st, buckets + (size_t)lvl_off * XB, cnt);
-        }
+      const uint32_t lvl_off = lv.off[l], cnt = lv.cnt[l];
+      if (!top_fused || cnt > top_max) vt->pair(st, buckets + (size_t)lvl_off * XB, buckets + (size_t)lv.off[l + 1] * XB, S * cnt / 2);
+      else if ((cnt == top_max || l == 0) && l != l_top) {         // this level and all above it, in a launch of its own
+        ZKP_REQUIRE(S == 1, ZKP_ERR_BAD_ARG);
+        vt->pair_top(st, buckets + (size_t)lvl_off * XB, cnt);
       }
       plan.first_block[l] = blocks;
       plan.off[l] = lvl_off + 1;
       plan.stride[l] = 2;
       plan.count[l] = cnt / 2;
+      plan.set_step[l] = lv.step[l];
       blocks += (cnt / 2 + chunk - 1) / chunk;
-      lvl_off = next_off;
-      cnt /= 2;
     }
     plan.first_block[L] = blocks;
-    const char* root = buckets + (size_t)lvl_off * XB;      // cnt == 1
-    char* partial = reinterpret_cast<char*>(ws.tmp.get(((size_t)blocks + 64) * XB));
-    char* Obuf = partial + (size_t)blocks * XB;
+    const char* root = buckets + (size_t)lv.off[L] * XB;    // the root of set g lies lv.step[L] entries further on
+    ZKP_REQUIRE(S == 1 || (L > 0 && l_top >= 0), ZKP_ERR_BAD_ARG);
+    char* partial = reinterpret_cast<char*>(ws.tmp.get((size_t)S * ((size_t)blocks + 64) * XB));
+    char* Obuf = partial + (size_t)S * blocks * XB;        // L sums per set
     if (L > 0 && l_top >= 0) {
       SegPlan low = plan;                                    // levels 0 .. l_top - 1: complete before this launch
       low.L = l_top;
       const uint32_t blocks_low = plan.first_block[l_top];
-      vt->pair_top_segsum(st, top_base, top_cnt, buckets, &low, partial, blocks_low);
+      vt->pair_top_segsum(st, top_base, top_cnt, buckets, &low, partial, blocks_low, S);
       SegPlan p2{};
       p2.L = L;
       p2.chunk = chunk;
@@ -1202,17 +1236,19 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
           p2.off[l] = plan.first_block[l];
           p2.stride[l] = 1;
           p2.count[l] = plan.first_block[l + 1] - plan.first_block[l];
+          p2.set_step[l] = blocks_low;                       // set g's partials follow those of set g - 1
         } else {                                             // the level's odd entries themselves
           p2.off[l] = plan.off[l];
           p2.stride[l] = plan.stride[l];
           p2.count[l] = plan.count[l];
+          p2.set_step[l] = plan.set_step[l];
         }
         ZKP_REQUIRE(p2.count[l] <= chunk, ZKP_ERR_BAD_ARG);
       }
       p2.first_block[L] = L;
-      vt->segsum(st, partial, &p2, Obuf, L, buckets, l_top);
+      vt->segsum(st, partial, &p2, Obuf, L, buckets, l_top, S);
     } else if (L > 0) {
-      vt->segsum(st, buckets, &plan, partial, blocks, nullptr, 1 << 30);
+      vt->segsum(st, buckets, &plan, partial, blocks, nullptr, 1 << 30, 1);
       SegPlan p2{};
       p2.L = L;
       p2.chunk = chunk;
@@ -1224,9 +1260,9 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
         ZKP_REQUIRE(p2.count[l] <= chunk, ZKP_ERR_BAD_ARG);
       }
       p2.first_block[L] = L;
-      vt->segsum(st, partial, &p2, Obuf, L, nullptr, 1 << 30);
+      vt->segsum(st, partial, &p2, Obuf, L, nullptr, 1 << 30, 1);
     }
-    vt->final(st, Obuf, L, root, (char*)out_dev_xyzz, out_jac);
+    vt->final(st, Obuf, L, root, (char*)out_dev_xyzz, out_jac, S, lv.step[L], out_stride, (uint32_t)jac_words);
     ctx->mark(st, ":reduced");
   }
   ZKP_HIP(hipGetLastError());

@@ -74,10 +74,11 @@ __global__ __launch_bounds__(256) void pair_kernel(const char* __restrict__ in, 
 // the hardware queue instead of ten (streams that share the queue wait behind every packet).
 constexpr int PAIR_TOP_THREADS = 512;
 template <class F>
-__device__ __forceinline__ void pair_top_body(char* __restrict__ base, uint32_t cnt) {
-  char* in = base;
+__device__ __forceinline__ void pair_top_body(char* __restrict__ base, uint32_t cnt, uint32_t set, uint32_t sets) {
+  // set g of `sets` side by side at `base`: its levels go to a region of cnt entries behind all of them (sets == 1: directly behind)
+  char* in = base + (size_t)set * cnt * BkPoint<F>::BYTES;
+  char* out = base + (size_t)(sets + set) * cnt * BkPoint<F>::BYTES;
   for (; cnt > 1; cnt >>= 1) {
-    char* out = in + (size_t)cnt * BkPoint<F>::BYTES;
     bool coop = false;
     if constexpr (QuadCoop<F>::ON) coop = cnt / 2 <= PAIR_TOP_THREADS / 4;       // fewer additions than quads: four lanes per addition
     if constexpr (QuadCoop<F>::ON) {
@@ -95,12 +96,13 @@ __device__ __forceinline__ void pair_top_body(char* __restrict__ base, uint32_t 
     __threadfence_block();
     __syncthreads();
     in = out;
+    out = in + (size_t)(cnt / 2) * BkPoint<F>::BYTES;
   }
 }
 template <class F>
 __global__ __launch_bounds__(PAIR_TOP_THREADS) void pair_top_kernel(char* __restrict__ base, uint32_t cnt) {
   __builtin_amdgcn_s_setprio(3);
-  pair_top_body<F>(base, cnt);
+  pair_top_body<F>(base, cnt, 0, 1);
 }
 
 // One block of a segmented sum: block -> (segment l, chunk); sums <= plan.chunk entries into partial[block].  Segments l >= l_hi read
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(PAIR_TOP_THREADS) void pair_top_kernel(char* __rest
 // levels the fused top produced).  Written for workgroups of >= 256 threads: threads >= 256 only take part in the barriers.
 template <class F>
 __device__ __forceinline__ void segsum_body(const char* __restrict__ base, const SegPlan& plan, char* __restrict__ partial, uint32_t block,
-                                            const char* __restrict__ base_hi, int l_hi) {
+                                            const char* __restrict__ base_hi, int l_hi, uint32_t set, uint32_t set_blocks) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t t = threadIdx.x;
   const bool act = t < 256;
@@ -118,13 +120,15 @@ __device__ __forceinline__ void segsum_body(const char* __restrict__ base, const
   uint32_t chunk = block - plan.first_block[l];
   uint32_t lo = chunk * plan.chunk;
   uint32_t hi = min(plan.count[l], lo + plan.chunk);
+  const size_t off = (size_t)plan.off[l] + (size_t)set * plan.set_step[l];       // this set's segment
+  partial += (size_t)set * set_blocks * BkPoint<F>::BYTES;                        // and its run of partials
   if constexpr (BkPoint<F>::MEM_ADD) {
     // the running sum lives in this thread's LDS slot and every addition streams its operands (BkPoint::add_mem)
     char* my = smem + (act ? t : 0) * BkPoint<F>::BYTES;
     if (act) {
       BkPoint<F>::inf().store(my);
       for (uint32_t i = lo + t; i < hi; i += 256)
-        BkPoint<F>::add_mem(my, base + ((size_t)plan.off[l] + (size_t)i * plan.stride[l]) * BkPoint<F>::BYTES, my);
+        BkPoint<F>::add_mem(my, base + (off + (size_t)i * plan.stride[l]) * BkPoint<F>::BYTES, my);
     }
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -145,7 +149,7 @@ __device__ __forceinline__ void segsum_body(const char* __restrict__ base, const
   BkPoint<F> acc = BkPoint<F>::inf();
   if (act) {
     for (uint32_t i = lo + t; i < hi; i += 256)
-      acc.add(BkPoint<F>::load(base + ((size_t)plan.off[l] + (size_t)i * plan.stride[l]) * BkPoint<F>::BYTES));
+      acc.add(BkPoint<F>::load(base + (off + (size_t)i * plan.stride[l]) * BkPoint<F>::BYTES));
     // LDS tree
     acc.store(smem + t * BkPoint<F>::BYTES);
   }
@@ -166,7 +170,7 @@ template <class F>
 __global__ __launch_bounds__(256) void segsum_kernel(const char* __restrict__ base, SegPlan plan, char* __restrict__ partial,
                                                      const char* __restrict__ base_hi, int l_hi) {
   __builtin_amdgcn_s_setprio(3);   // latency-bound tail: win issue arbitration against co-resident accumulate waves
-  segsum_body<F>(base, plan, partial, blockIdx.x, base_hi, l_hi);
+  segsum_body<F>(base, plan, partial, blockIdx.x, base_hi, l_hi, blockIdx.y, gridDim.x);
 }
 // Round 6: the top of the pyramid (ONE workgroup, ~85 us of dependent additions) and the segmented sums of every level below it
 // (hundreds of workgroups, ~105 us) depend on disjoint data — in ONE launch they run side by side instead of one after the other:
@@ -177,10 +181,10 @@ __global__ __launch_bounds__(PAIR_TOP_THREADS) void pair_top_segsum_kernel(char*
                                                                            char* __restrict__ partial) {
   __builtin_amdgcn_s_setprio(3);
   if (blockIdx.x == 0) {
-    pair_top_body<F>(top_base, top_cnt);
+    pair_top_body<F>(top_base, top_cnt, blockIdx.y, gridDim.y);
     return;
   }
-  segsum_body<F>(base, plan, partial, blockIdx.x - 1, nullptr, 1 << 30);
+  segsum_body<F>(base, plan, partial, blockIdx.x - 1, nullptr, 1 << 30, blockIdx.y, gridDim.x - 1);
 }
 
 // Buckets split into up to COMBINE_SMALL tasks are folded by ONE lane each (64 buckets per wave-addition); only genuinely long
@@ -254,10 +258,16 @@ __global__ __launch_bounds__(256) void combine_kernel(const uint32_t* __restrict
 // out = sum_l 2^l * O[l] + root ; one wave
 template <class F>
 __global__ __launch_bounds__(128) void final_kernel(const char* __restrict__ O, int L, const char* __restrict__ root,
-                                                   char* __restrict__ out_xyzz, uint32_t* __restrict__ out_jac) {
+                                                   char* __restrict__ out_xyzz, uint32_t* __restrict__ out_jac, uint32_t root_step,
+                                                   size_t out_stride, uint32_t jac_words) {
   __builtin_amdgcn_s_setprio(3);   // latency-bound tail: win issue arbitration against co-resident accumulate waves
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int t = threadIdx.x;
+  // one workgroup per bucket set of a fused MSM
+  O += (size_t)blockIdx.x * L * BkPoint<F>::BYTES;
+  root += (size_t)blockIdx.x * root_step * BkPoint<F>::BYTES;
+  if (out_xyzz) out_xyzz += (size_t)blockIdx.x * out_stride;
+  if (out_jac) out_jac += (size_t)blockIdx.x * jac_words;
   if constexpr (QuadCoop<F>::ON && QuadCoop<F>::GROUP == 1) {
     // G1 (round 4): 128 lanes = 32 quads, quad q owns point q (levels 0..L-1, the root at L): q cooperative doublings, then a tree
     // of cooperative additions — 18 x 3 + 5 x 5.5 product latencies instead of 18 x 9.75 + 6 x 14.5
@@ -395,11 +405,11 @@ __global__ __launch_bounds__(256) void final_var_kernel(const char* __restrict__
 }
 
 template <class F>
-__global__ void write_identity_kernel(char* out_xyzz, uint32_t* out_jac) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
+__global__ void write_identity_kernel(char* out_xyzz, uint32_t* out_jac, size_t out_stride, uint32_t jac_words) {
+  if (threadIdx.x == 0) {                                   // one workgroup per result
     XYZZ<F> z = XYZZ<F>::inf();
-    if (out_xyzz) z.store(out_xyzz);
-    if (out_jac) z.store_jacobian(out_jac);
+    if (out_xyzz) z.store(out_xyzz + (size_t)blockIdx.x * out_stride);
+    if (out_jac) z.store_jacobian(out_jac + (size_t)blockIdx.x * jac_words);
   }
 }
 
@@ -842,6 +852,11 @@ __global__ __launch_bounds__(128) void assemble_g1_part1_kernel(char* __restrict
   constexpr int NB = G::BITS;                                  // doubling-chain length: bits of |k1|, |k2|
   constexpr size_t JB = 3 * 4 * F::N;                          // bytes of a Jacobian point
   const int t = threadIdx.x, chain = t >> 6, lane = t & 63;
+  // one workgroup per proof of a fused group (msm_vtbl.hpp)
+  res += (size_t)blockIdx.x * 6 * slot;
+  rs += (size_t)blockIdx.x * 16;
+  if (out) out += (size_t)blockIdx.x * ASM_OUT_STEP;
+  flags += (size_t)blockIdx.x * 4;
   char* D = smem + (size_t)chain * NB * JB;                    // D[k] = 2^k * P (Jacobian)
   char* red = smem + 2 * NB * JB + (size_t)chain * 64 * XYZZ<F>::BYTES;
   // chain 0: g_a (slot 0) times s ; chain 1: g1_b (slot 1) times r
@@ -910,7 +925,10 @@ __global__ __launch_bounds__(64) void assemble_g1_part2_kernel(char* __restrict_
                                                                uint32_t* __restrict__ out,
                                                                uint32_t* __restrict__ flags, int c_off_words) {
   using F = CfgF;
-  if (threadIdx.x || blockIdx.x) return;
+  if (threadIdx.x) return;
+  res += (size_t)blockIdx.x * 6 * slot;                        // one workgroup per proof of a fused group
+  if (out) out += (size_t)blockIdx.x * ASM_OUT_STEP;
+  flags += (size_t)blockIdx.x * 4;
   XYZZ<F> acc = XYZZ<F>::load(res + 5 * slot);
   acc.add(XYZZ<F>::load(res + 3 * slot));
   acc.add(XYZZ<F>::load(res + 4 * slot));
@@ -926,7 +944,10 @@ __global__ __launch_bounds__(64) void assemble_g1_part2_kernel(char* __restrict_
 __global__ __launch_bounds__(64) void assemble_g2_kernel(const char* __restrict__ res, size_t slot,
                                                          uint32_t* __restrict__ out, uint32_t* __restrict__ flags,
                                                          int out_off_words) {
-  if (threadIdx.x || blockIdx.x) return;
+  if (threadIdx.x) return;
+  res += (size_t)blockIdx.x * 6 * slot;                        // one workgroup per proof of a fused group
+  out += (size_t)blockIdx.x * ASM_OUT_STEP;
+  flags += (size_t)blockIdx.x * 4;
   XYZZ<CfgF> p = XYZZ<CfgF>::load(res + 2 * slot);
   p.to_affine().store(out + out_off_words);
   flags[1] = p.is_inf() ? 1 : 0;
@@ -959,20 +980,23 @@ void l_pair(hipStream_t s, const char* in, char* out, uint32_t count) {
 void l_pair_top(hipStream_t s, char* base, uint32_t count) {
   hipLaunchKernelGGL(pair_top_kernel<F>, dim3(1), dim3(PAIR_TOP_THREADS), 0, s, base, count);
 }
-void l_segsum(hipStream_t s, const char* base, const SegPlan* plan, char* partial, uint32_t blocks, const char* base_hi, int l_hi) {
-  hipLaunchKernelGGL(segsum_kernel<F>, dim3(blocks), dim3(256), 256 * BB, s, base, *plan, partial, base_hi, l_hi);
+void l_segsum(hipStream_t s, const char* base, const SegPlan* plan, char* partial, uint32_t blocks, const char* base_hi, int l_hi,
+              uint32_t sets) {
+  hipLaunchKernelGGL(segsum_kernel<F>, dim3(blocks, sets), dim3(256), 256 * BB, s, base, *plan, partial, base_hi, l_hi);
 }
 void l_pair_top_segsum(hipStream_t s, char* top_base, uint32_t top_cnt, const char* base, const SegPlan* plan, char* partial,
-                       uint32_t blocks) {
-  hipLaunchKernelGGL(pair_top_segsum_kernel<F>, dim3(1 + blocks), dim3(PAIR_TOP_THREADS), 256 * BB, s, top_base, top_cnt, base, *plan,
-                     partial);
+                       uint32_t blocks, uint32_t sets) {
+  hipLaunchKernelGGL(pair_top_segsum_kernel<F>, dim3(1 + blocks, sets), dim3(PAIR_TOP_THREADS), 256 * BB, s, top_base, top_cnt, base,
+                     *plan, partial);
 }
-void l_final(hipStream_t s, const char* O, int L, const char* root, char* out_xyzz, uint32_t* out_jac) {
+void l_final(hipStream_t s, const char* O, int L, const char* root, char* out_xyzz, uint32_t* out_jac, uint32_t sets,
+             uint32_t root_step, size_t out_stride, uint32_t jac_words) {
   constexpr int threads = (QuadCoop<F>::ON && QuadCoop<F>::GROUP == 1) ? 128 : 64;            // G1: 32 quads (coop_dev.hpp)
-  hipLaunchKernelGGL(final_kernel<F>, dim3(1), dim3(threads), 64 * BB, s, O, L, root, out_xyzz, out_jac);
+  hipLaunchKernelGGL(final_kernel<F>, dim3(sets), dim3(threads), 64 * BB, s, O, L, root, out_xyzz, out_jac, root_step, out_stride,
+                     jac_words);
 }
-void l_identity(hipStream_t s, char* out_xyzz, uint32_t* out_jac) {
-  hipLaunchKernelGGL(write_identity_kernel<F>, dim3(1), dim3(64), 0, s, out_xyzz, out_jac);
+void l_identity(hipStream_t s, char* out_xyzz, uint32_t* out_jac, uint32_t sets, size_t out_stride, uint32_t jac_words) {
+  hipLaunchKernelGGL(write_identity_kernel<F>, dim3(sets), dim3(64), 0, s, out_xyzz, out_jac, out_stride, jac_words);
 }
 void l_fold(hipStream_t s, const uint32_t* pts, int k, uint32_t* out_jac) {
   hipLaunchKernelGGL(fold_kernel<F>, dim3(1), dim3(64), 0, s, pts, k, out_jac);
@@ -1030,16 +1054,16 @@ void l_fixed_base(hipStream_t s, const uint32_t* base, const uint32_t* scalars, 
                      out_xy, out_inf);
 }
 #if ZKP_CFG_GROUP == 1
-void l_assemble_g1_p1(hipStream_t s, char* res, size_t slot, const uint32_t* rs, uint32_t* out, uint32_t* flags) {
+void l_assemble_g1_p1(hipStream_t s, char* res, size_t slot, const uint32_t* rs, uint32_t* out, uint32_t* flags, uint32_t proofs) {
   const size_t lds = 2 * (size_t)GlvConst<CfgFq>::BITS * 3 * 4 * F::N + 2 * 64 * XB;
-  hipLaunchKernelGGL(assemble_g1_part1_kernel, dim3(1), dim3(128), lds, s, res, slot, rs, out, flags);
+  hipLaunchKernelGGL(assemble_g1_part1_kernel, dim3(proofs), dim3(128), lds, s, res, slot, rs, out, flags);
 }
-void l_assemble_g1_p2(hipStream_t s, char* res, size_t slot, uint32_t* out, uint32_t* flags, int c_off_words) {
-  hipLaunchKernelGGL(assemble_g1_part2_kernel, dim3(1), dim3(64), 0, s, res, slot, out, flags, c_off_words);
+void l_assemble_g1_p2(hipStream_t s, char* res, size_t slot, uint32_t* out, uint32_t* flags, int c_off_words, uint32_t proofs) {
+  hipLaunchKernelGGL(assemble_g1_part2_kernel, dim3(proofs), dim3(64), 0, s, res, slot, out, flags, c_off_words);
 }
 #else
-void l_assemble_g2(hipStream_t s, const char* res, size_t slot, uint32_t* out, uint32_t* flags, int off) {
-  hipLaunchKernelGGL(assemble_g2_kernel, dim3(1), dim3(64), 0, s, res, slot, out, flags, off);
+void l_assemble_g2(hipStream_t s, const char* res, size_t slot, uint32_t* out, uint32_t* flags, int off, uint32_t proofs) {
+  hipLaunchKernelGGL(assemble_g2_kernel, dim3(proofs), dim3(64), 0, s, res, slot, out, flags, off);
 }
 #endif
 }  // namespace

@@ -23,6 +23,7 @@ struct SegPlan {
   uint32_t off[25];            // element offset of segment l's first entry
   uint32_t stride[25];         // element stride
   uint32_t count[25];          // entries in segment l
+  uint32_t set_step[25];       // fused MSMs (msm.hip `sets`): set g's segment l starts g * set_step[l] elements behind set 0's
 };
 
 // one block of a descriptor-driven segmented sum: out[d.out] = sum_{i < count} base[off + i * stride]
@@ -53,9 +54,13 @@ struct MsmVtbl {
                   const char* partial, char* buckets, uint32_t init);   // init: add the bucket's stored value too
   void (*pair)(hipStream_t, const char* in, char* out, uint32_t count);
   // segments l >= l_hi read from base_hi instead of base (pass nullptr, 1 << 30 for a plain segmented sum)
-  void (*segsum)(hipStream_t, const char* base, const SegPlan* plan, char* partial, uint32_t blocks, const char* base_hi, int l_hi);
-  void (*final)(hipStream_t, const char* O, int L, const char* root, char* out_xyzz, uint32_t* out_jac);
-  void (*write_identity)(hipStream_t, char* out_xyzz, uint32_t* out_jac);
+  // sets: bucket sets of a fused MSM, one per blockIdx.y; `blocks` and the plan are per set, set g writes partial[g * blocks + block]
+  void (*segsum)(hipStream_t, const char* base, const SegPlan* plan, char* partial, uint32_t blocks, const char* base_hi, int l_hi,
+                 uint32_t sets);
+  // one workgroup per set g: O + g * L, root + g * root_step points; results out_stride bytes / jac_words words apart
+  void (*final)(hipStream_t, const char* O, int L, const char* root, char* out_xyzz, uint32_t* out_jac, uint32_t sets,
+                uint32_t root_step, size_t out_stride, uint32_t jac_words);
+  void (*write_identity)(hipStream_t, char* out_xyzz, uint32_t* out_jac, uint32_t sets, size_t out_stride, uint32_t jac_words);
   void (*fold)(hipStream_t, const uint32_t* pts, int k, uint32_t* out_jac);
   void (*into_affine)(hipStream_t, const uint32_t* jac, uint32_t* xy, uint32_t* inf);
   // k points at once, one lane each: out_i = affine(a_i + b_i) (b_i Jacobian too; has_b[i] == 0: a_i alone) — the k
@@ -80,11 +85,14 @@ struct MsmVtbl {
   // Groth16 assembly (groth16.hip): G1 tables implement assemble_g1, G2 tables assemble_g2
   // part 1 needs only g_a (slot 0) and g1_b (slot 1): proof.a = affine(g_a); T = s*g_a + r*g1_b -> slot 5.
   // part 2: C = T + h_acc (slot 3) + l' (slot 4) -> affine.  Split so part 1 overlaps the remaining MSMs.
-  void (*assemble_g1_part1)(hipStream_t, char* res, size_t slot, const uint32_t* rs, uint32_t* out, uint32_t* flags);
-  void (*assemble_g1_part2)(hipStream_t, char* res, size_t slot, uint32_t* out, uint32_t* flags, int c_off_words);
-  void (*assemble_g2)(hipStream_t, const char* res, size_t slot, uint32_t* out, uint32_t* flags, int out_off_words);
+  // proofs: one workgroup per proof of a fused group; proof g has its 6 slots at res + g * 6 * slot, [r, s] at rs + 16 g, its
+  // proof words at out + ASM_OUT_STEP * g and its flags at flags + 4 g
+  void (*assemble_g1_part1)(hipStream_t, char* res, size_t slot, const uint32_t* rs, uint32_t* out, uint32_t* flags, uint32_t proofs);
+  void (*assemble_g1_part2)(hipStream_t, char* res, size_t slot, uint32_t* out, uint32_t* flags, int c_off_words, uint32_t proofs);
+  void (*assemble_g2)(hipStream_t, const char* res, size_t slot, uint32_t* out, uint32_t* flags, int out_off_words, uint32_t proofs);
   // the top of the pairwise pyramid in one launch: levels from the one with `count` (<= PAIR_TOP_MAX; 1024: 129.4, 2048: 130.1, 4096: 129.5 proofs/s) entries at `base` down to
-  // the root, each level stored directly behind its predecessor
+  // the root, each level stored directly behind its predecessor.  With `sets` > 1 (pair_top_segsum) the level at `base` holds the
+  // sets side by side; set g's first output level goes to base + (sets + g) * count, a region of its own, the rest behind it
   void (*pair_top)(hipStream_t, char* base, uint32_t count);
   // group-element transform of a base vector (msm_group.hip "group-element transform"; groth16.hip: the H query in evaluation form):
   // out_j = sum_i tw^(ij) (scal_i * P_i), i, j < 2^log_n; scal / tw: canonical 8-word scalars (tw: 2^(log_n-1) powers);
@@ -96,9 +104,10 @@ struct MsmVtbl {
                 const uint8_t* kind, const uint32_t* coeff, const char* G_xy, const uint8_t* G_inf, char* out_xy, uint8_t* out_inf);
   // pair_top on (top_base, top_cnt) and the segmented sums of `plan` over `base` in ONE launch (block 0 | blocks 1..blocks)
   void (*pair_top_segsum)(hipStream_t, char* top_base, uint32_t top_cnt, const char* base, const SegPlan* plan, char* partial,
-                          uint32_t blocks);
+                          uint32_t blocks, uint32_t sets);
 };
 constexpr uint32_t PAIR_TOP_MAX = 2048;
+constexpr uint32_t ASM_OUT_STEP = 256;     // words between the device proofs of a fused group (groth16.hip)
 
 const MsmVtbl* msm_vtbl(int curve, int group);     // msm.hip; throws StatusError on unknown config
 

@@ -570,7 +570,8 @@ int32_t zkp_groth16_domain_size(zkp_groth16_pk* pk, uint64_t* n);
 /* Window-table plan of a resident key: info[0] = window-group size k (1 = one table copy per window; > 1: the tables did not
  * fit ZKP_TABLE_BUDGET_GB / the free device memory and k consecutive windows share a copy), info[1] = bytes of the five
  * queries' tables, info[2..4] = window bits / windows / resident copies of the A query, info[5] = window bits of the B queries,
- * info[6] = sort sharing (bit 0: B1 reuses B2's bucket sort, bit 1: L reuses A's, bit 2: shared level-1 pass), info[7] = key form (bit 0: H query in evaluation form, bit 1: C folded into the L query, bit 2: L and H
+ * info[6] = sort sharing (bit 0: B1 reuses B2's bucket sort, bit 1: L reuses A's, bit 2: shared level-1 pass; bits 32..63: how many
+ * fused proof groups the pipelined batches of this key have run so far, warm-up groups left out), info[7] = key form (bit 0: H query in evaluation form, bit 1: C folded into the L query, bit 2: L and H
  * bucket-chained).  With any bit of info[7] set, slots L (3) and H (4) of zkp_groth16_prove_partials_dev are NOT the reference's
  * l_aux_acc / h_acc individually — only slot 3 + slot 4 equals l_aux_acc + h_acc, which is all prover.rs:189-196 consumes
  * (ZKP_H_LAGRANGE=0 ZKP_C_FOLD=0 ZKP_CHAIN_LH=0 at upload restores the individual values). */

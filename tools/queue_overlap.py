@@ -3,12 +3,14 @@
 rocprofv3 kernel-trace database of `bench.py --gpus 1 --steps K --warmup W`.
 
     rocprofv3 --kernel-trace -d DIR -o t -- python bench.py --gpus 1 --steps 24 --warmup 8
-    python tools/queue_overlap.py DIR/.../t_results.db [--steps 24] [--lanes 8] [--label before]
+    python tools/queue_overlap.py DIR/.../t_results.db [--steps 24] [--lanes 8] [--group 1] [--label before]
 
 Proofs are delimited by the launches of assemble_g1_part2_kernel: one per proof, the last kernel on the proof's main stream.  The
 streams that launch prover kernels are grouped four by four in the order of their ids (a lane's four streams are created
 together); a proof is everything its lane's streams start after the lane's previous part 2 and up to its own.  The timed batch is
 the last K proofs; the steady-state window leaves out its first and last `lanes` proofs (pipeline fill and drain).
+With fused proof groups (groth16.hip ZKP_PROOF_FUSE) one part 2 launch closes --group proofs: the units between two launches are
+groups, K / group of them are timed, `lanes` groups are left out at either end, and the per-proof figures divide by the group size.
 
 Prints, for that window: per hardware-queue id the stream ids seen on it in order of first use (and which lane / role each is),
 the union coverage of the accumulate_kernel intervals, the largest number of kernels in flight, and for every pair of consecutive
@@ -64,11 +66,13 @@ def union(intervals, a, b):
     return busy, peak
 
 
-def analyse(rows, steps, lanes, label):
+def analyse(rows, steps, lanes, label, group=1):
     out = []
     part2 = [r for r in rows if "assemble_g1_part2_kernel" in r[0]]
+    proofs_timed = steps
+    steps = steps // group                                   # units (groups of `group` proofs) from here on
     if len(part2) < steps:
-        raise SystemExit(f"{len(part2)} assemble_g1_part2_kernel launches in the trace, fewer than --steps {steps}")
+        raise SystemExit(f"{len(part2)} assemble_g1_part2_kernel launches in the trace, fewer than --steps {proofs_timed} / --group {group}")
     t_first = part2[-steps][1]
     # the streams of the prover: whatever launched an accumulate or either half of the assembly during the timed batch
     prover = sorted({st for n, s, e, q, st in rows if s >= t_first - 5e7 and
@@ -100,8 +104,12 @@ def analyse(rows, steps, lanes, label):
     sel = [r for r in rows if r[2] > a and r[1] < b]
     wall = b - a
     out.append(f"## {label}")
-    out.append(f"timed batch: the last {steps} of {len(part2)} proofs in the trace; steady-state window: proofs {skip + 1}..{len(timed) - skip} "
-               f"of the batch, {wall / 1e6:.2f} ms, {len(steady)} proofs = {wall / 1e6 / len(steady):.3f} ms per proof under the tracer")
+    unit = "proofs" if group == 1 else f"groups of {group} proofs"
+    n_proofs = len(steady) * group
+    out.append(f"timed batch: the last {steps} of {len(part2)} {unit} in the trace; steady-state window: {unit} {skip + 1}..{len(timed) - skip} "
+               f"of the batch, {wall / 1e6:.2f} ms, {n_proofs} proofs = {wall / 1e6 / n_proofs:.3f} ms per proof under the tracer")
+    launches = sum(1 for r in sel if r[4] in lane_of and "copyBuffer" not in r[0])
+    out.append(f"kernel launches on the prover's streams in the window (copies left out): {launches} = {launches / n_proofs:.1f} per proof")
     out.append(f"prover streams: {len(prover)} in {n_lanes} lanes (ids {prover[0]}..{prover[-1]})" if prover else "no prover streams")
 
     # --- placement
@@ -168,6 +176,7 @@ if __name__ == "__main__":
     ap.add_argument("db")
     ap.add_argument("--steps", type=int, default=24, help="timed proofs of the traced bench run")
     ap.add_argument("--lanes", type=int, default=8, help="proofs left out at either end of the timed batch")
+    ap.add_argument("--group", type=int, default=1, help="proofs closed by one assemble_g1_part2_kernel launch (fused groups)")
     ap.add_argument("--label", default="trace")
     a = ap.parse_args()
-    print(analyse(load(a.db), a.steps, a.lanes, a.label))
+    print(analyse(load(a.db), a.steps, a.lanes, a.label, a.group))
