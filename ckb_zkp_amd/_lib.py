@@ -95,6 +95,12 @@ def make_config(config) -> "CtxConfig | None":
     return cfg
 
 
+class BpVectors(C.Structure):
+    """zkp_bp_vectors (include/zkp_accel.h): the inputs of l(X) and r(X), device pointers and lengths"""
+    _fields_ = [("aL", vp), ("aR", vp), ("aO", vp), ("w", vp), ("v", vp), ("sL", vp), ("sR", vp),
+                ("n", C.c_size_t), ("n_w", C.c_size_t), ("n_s", C.c_size_t), ("N", C.c_size_t)]
+
+
 MARLIN_NUM_EVALS = 21
 
 
@@ -163,6 +169,10 @@ SIGNATURES = {
     "zkp_fr_gkr_round_dev": (C.c_int32, [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, vp]),
     "zkp_fr_gkr_eval_layer_batch_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, C.c_size_t]),
     "zkp_fr_gkr_dp_round_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]),
+    "zkp_fr_powers_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, C.c_size_t]),
+    "zkp_fr_bp_t_coeffs_dev": (C.c_int32, [vp, C.c_int, C.POINTER(BpVectors), vp, vp, vp]),
+    "zkp_fr_bp_lr_eval_dev": (C.c_int32, [vp, C.c_int, C.POINTER(BpVectors), vp, vp, vp, vp, vp, vp]),
+    "zkp_fr_ipa_fold_ab_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp, vp]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

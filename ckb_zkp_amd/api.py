@@ -366,6 +366,38 @@ class Context:
                                                     C.c_void_p(finals_ptr or 0)), "zkp_fr_gkr_dp_round_dev")
         return out
 
+    def fr_powers_dev(self, curve, first, ratio, out_ptr: int, n: int):
+        """zkp_fr_powers_dev: out[i] = first ratio^i for i < n into DEVICE memory; first, ratio: one Montgomery Fr (4 x u64) each."""
+        _lib.check(self.lib.zkp_fr_powers_dev(self.h, get_curve(curve).cid, _ptr(_c64(first)), _ptr(_c64(ratio)), C.c_void_p(out_ptr or 0), n),
+                   "zkp_fr_powers_dev")
+
+    @staticmethod
+    def bp_vectors(aL: int, aR: int, aO: int, w: int, v: int, sL: int, sR: int, n: int, n_w: int, n_s: int, N: int) -> "_lib.BpVectors":
+        """zkp_bp_vectors from DEVICE pointers (None / 0 where the length is 0) and lengths"""
+        return _lib.BpVectors(aL or None, aR or None, aO or None, w or None, v or None, sL or None, sR or None, n, n_w, n_s, N)
+
+    def fr_bp_t_coeffs_dev(self, curve, vecs, y, z) -> np.ndarray:
+        """zkp_fr_bp_t_coeffs_dev: t2 .. t10 of <l(X), r(X)> as (9, 4) uint64 Montgomery; vecs: bp_vectors(...); y, z: Montgomery Fr."""
+        out = np.zeros((9, 4), dtype=np.uint64)
+        _lib.check(self.lib.zkp_fr_bp_t_coeffs_dev(self.h, get_curve(curve).cid, C.byref(vecs), _ptr(_c64(y)), _ptr(_c64(z)), _ptr(out)),
+                   "zkp_fr_bp_t_coeffs_dev")
+        return out
+
+    def fr_bp_lr_eval_dev(self, curve, vecs, y, z, x, l_x_ptr: int, r_x_ptr: int) -> np.ndarray:
+        """zkp_fr_bp_lr_eval_dev: l(x) and r(x) into the DEVICE buffers of N Fr each; returns t_x = <l(x), r(x)> ((4,) Montgomery)."""
+        out = np.zeros(4, dtype=np.uint64)
+        _lib.check(self.lib.zkp_fr_bp_lr_eval_dev(self.h, get_curve(curve).cid, C.byref(vecs), _ptr(_c64(y)), _ptr(_c64(z)), _ptr(_c64(x)),
+                                                  C.c_void_p(l_x_ptr or 0), C.c_void_p(r_x_ptr or 0), _ptr(out)), "zkp_fr_bp_lr_eval_dev")
+        return out
+
+    def fr_ipa_fold_ab_dev(self, curve, a_ptr: int, b_ptr: int, n: int, x, want_c: bool = True):
+        """zkp_fr_ipa_fold_ab_dev: a[j] = x a[j] + x^-1 a[j + n/2], b[j] = x^-1 b[j] + x b[j + n/2] in place over DEVICE Montgomery Fr.
+        Returns the next round's (cL, cR) as (2, 4) uint64 Montgomery, or None without want_c or when n == 2."""
+        out = np.zeros((2, 4), dtype=np.uint64) if want_c and n > 2 else None
+        _lib.check(self.lib.zkp_fr_ipa_fold_ab_dev(self.h, get_curve(curve).cid, C.c_void_p(a_ptr or 0), C.c_void_p(b_ptr or 0), n,
+                                                   _ptr(_c64(x)), _ptr(out)), "zkp_fr_ipa_fold_ab_dev")
+        return out
+
     def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
         """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
         Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""

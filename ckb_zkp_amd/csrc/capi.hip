@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "bulletproofs.hpp"
 #include "ctx.hpp"
 #include "gkr.hpp"
 #include "host_field.hpp"
@@ -542,6 +543,27 @@ int32_t zkp_fr_gkr_dp_round_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_l
                                 uint64_t* finals_dev) {
   if (!layer || !v_dev || !eq_dev || !w_dev || (!bind_host && !evals_out_host)) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { fr_gkr_dp_round(ctx, curve, layer, v_dev, eq_dev, w_dev, n, len, bind_host, evals_out_host, finals_dev); });
+}
+int32_t zkp_fr_powers_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* first_host, const uint64_t* ratio_host, uint64_t* out_dev,
+                          size_t n) {
+  if (n && (!first_host || !ratio_host || !out_dev)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_powers(ctx, curve, first_host, ratio_host, out_dev, n); });
+}
+int32_t zkp_fr_bp_t_coeffs_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_bp_vectors* vecs, const uint64_t* y_host,
+                               const uint64_t* z_host, uint64_t* t_out_host) {
+  if (!vecs || !y_host || !z_host || !t_out_host) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_bp_t_coeffs(ctx, curve, vecs, y_host, z_host, t_out_host); });
+}
+int32_t zkp_fr_bp_lr_eval_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_bp_vectors* vecs, const uint64_t* y_host,
+                              const uint64_t* z_host, const uint64_t* x_host, uint64_t* l_x_dev, uint64_t* r_x_dev,
+                              uint64_t* t_x_out_host) {
+  if (!vecs || !y_host || !z_host || !x_host || !l_x_dev || !r_x_dev || !t_x_out_host) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_bp_lr_eval(ctx, curve, vecs, y_host, z_host, x_host, l_x_dev, r_x_dev, t_x_out_host); });
+}
+int32_t zkp_fr_ipa_fold_ab_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* a_dev, uint64_t* b_dev, size_t n, const uint64_t* x_host,
+                               uint64_t* c_out_host) {
+  if (!a_dev || !b_dev || !x_host) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_ipa_fold_ab(ctx, curve, a_dev, b_dev, n, x_host, c_out_host); });
 }
 int32_t zkp_fr_prefix_product_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* in_dev, uint64_t* out_dev, size_t n,
                                   uint64_t* total_out_host) {

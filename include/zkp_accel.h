@@ -54,7 +54,8 @@ const char* zkp_status_string(int32_t status);
  * then zkp_gkr_layer_upload / _free / _info and zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev (Libra GKR),
  * then zkp_fr_prefix_product_dev / zkp_fr_plonk_perm_z_dev / zkp_fr_plonk_quotient_dev (PLONK rounds 2 and 3),
  * then zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev (PLONK evaluations and opening polynomials),
- * then zkp_fr_gkr_eval_layer_batch_dev / zkp_fr_gkr_dp_round_dev (Hyrax data-parallel GKR).
+ * then zkp_fr_gkr_eval_layer_batch_dev / zkp_fr_gkr_dp_round_dev (Hyrax data-parallel GKR),
+ * then zkp_fr_powers_dev / zkp_fr_bp_t_coeffs_dev / zkp_fr_bp_lr_eval_dev / zkp_fr_ipa_fold_ab_dev (Bulletproofs R1CS prover).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -380,6 +381,65 @@ int32_t zkp_fr_gkr_eval_layer_batch_dev(zkp_ctx* ctx, zkp_curve_t curve, const z
 int32_t zkp_fr_gkr_dp_round_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_gkr_layer* layer, uint64_t* v_dev, uint64_t* eq_dev,
                                 const uint64_t* w_dev, size_t n, size_t len, const uint64_t* bind_host, uint64_t* evals_out_host,
                                 uint64_t* finals_dev);
+/* The Bulletproofs R1CS prover (later in 0.7.1, detected by symbol): the Fr work of `prove` (bulletproofs/src/arithmetic_circuit.rs:
+ * 305-612) and of inner_product_proof::prove (inner_product_proof.rs:22-111), every vector kept on the device.  The commitments are
+ * zkp_msm_g1_var_batch_dev calls, the generator folds zkp_g1_ipa_fold_dev; the transcript stays with the caller.  Vectors: Fr,
+ * Montgomery, canonical, 16-byte aligned, device memory.  Scalars (*_host): Fr, Montgomery, < r, host memory.  Every element written is
+ * the canonical Montgomery representative (bit-exact results).  Every argument is checked before anything runs: on ZKP_ERR_BAD_ARG
+ * every output is untouched.  Each call runs on the context's current stream and returns when its outputs are written.
+ * A pass runs T = 256 * min(ceil(n / 256), 512) threads; thread j owns the indices j, j + T, ..., forms its powers once (one product
+ * per set bit of j, from the squarings base^(2^b) that the host passes) and steps by their T-th powers (computed on the host), the
+ * ownership of zkp_fr_poly_eval_many_dev.
+ *
+ * out[i] = first * ratio^i for i < n (y_n, z_Q of :411-433; z_Q is the vector zkp_fr_spmv_dev multiplies into the transposed
+ * constraint matrices).  One launch.  n == 0 -> ZKP_OK, nothing runs.  ratio == 0 gives [first, 0, ...].
+ * ZKP_ERR_BAD_ARG: a NULL or misaligned out_dev, n > 2^28, *first_host or *ratio_host >= r. */
+int32_t zkp_fr_powers_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* first_host, const uint64_t* ratio_host, uint64_t* out_dev,
+                          size_t n);
+/* The inputs of l(X) and r(X): the padded vectors of :399-409 without their padding.  An index at or beyond a vector's length counts
+ * as zero and is never dereferenced; a pointer whose length is 0 may be NULL.  N: a power of two, at least each length, <= 2^28.
+ * v is the caller's zQ * WV (:469), n_w elements. */
+typedef struct {
+  const uint64_t* aL; /* n elements */
+  const uint64_t* aR; /* n */
+  const uint64_t* aO; /* n */
+  const uint64_t* w;  /* n_w: the witness */
+  const uint64_t* v;  /* n_w */
+  const uint64_t* sL; /* n_s: the blinding vectors */
+  const uint64_t* sR; /* n_s */
+  size_t n;
+  size_t n_w;
+  size_t n_s;
+  size_t N;
+} zkp_bp_vectors;
+/* The coefficients t2 .. t10 of t(X) = <l(X), r(X)> (VecPoly5::special_inner_product, bulletproofs/src/lib.rs:223-250), t4 included:
+ * t_out_host receives 9 Fr.  With the diagonal WL, WR, WO of :436-445 written out, for i < N:
+ *   Y_i = y^i,  Z_i = z^(i+1) for i < n else 0,  zn = z^n,  U_i = zn Z_i y^(-i)
+ *   l2 = aL + U,  l3 = aO,  l4 = w,  l5 = sL;    r0 = -v,  r1 = zn^2 Z - Y,  r2 = Y aR + Z,  r5 = Y sR      (:471-489)
+ * No coefficient vector is stored: one pass over the seven inputs forms them in registers (U as one progression of ratio z / y, y
+ * inverted once on the host) and leaves nine partial sums per workgroup, reduced three at a time through one LDS buffer; one small
+ * launch adds them.  Two launches.  ZKP_ERR_BAD_ARG: a NULL vecs, N not a power of two or > 2^28, a length above N, a NULL or
+ * misaligned vector of nonzero length, *y_host == 0, *y_host or *z_host >= r. */
+int32_t zkp_fr_bp_t_coeffs_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_bp_vectors* vecs, const uint64_t* y_host,
+                               const uint64_t* z_host, uint64_t* t_out_host);
+/* l(x) and r(x) (VecPoly5::eval, :528-529) from the same coefficients, formed again in registers, and t_x = <l(x), r(x)> (:531):
+ *   l_x[i] = x^2 (l2 + x (l3 + x (l4 + x l5))),   r_x[i] = r0 + x r1 + x^2 r2 + x^5 r5   for i < N;   *t_x_out_host = sum_i l_x[i] r_x[i].
+ * l_x_dev, r_x_dev: N Fr each; they overlap neither each other nor any input.  Two launches.
+ * ZKP_ERR_BAD_ARG: the rules of zkp_fr_bp_t_coeffs_dev, *x_host >= r, a NULL or misaligned output, an output that overlaps the
+ * other output or an input. */
+int32_t zkp_fr_bp_lr_eval_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_bp_vectors* vecs, const uint64_t* y_host,
+                              const uint64_t* z_host, const uint64_t* x_host, uint64_t* l_x_dev, uint64_t* r_x_dev,
+                              uint64_t* t_x_out_host);
+/* The a / b half of one round of inner_product_proof::prove (:93-95) together with the NEXT round's inner products (:54-55).
+ * n: a power of two, 2 <= n <= 2^28; m = n / 2.  In place over the low halves, the high halves [m, n) are left untouched:
+ *   a[j] = x a[j] + x^-1 a[j + m],   b[j] = x^-1 b[j] + x b[j + m]   for j < m.
+ * c_out_host != NULL and m >= 2: c_out_host[0] = cL = <a'[0, m/2), b'[m/2, m)>, c_out_host[1] = cR = <a'[m/2, m), b'[0, m/2)> of the
+ * folded vectors, formed in the same pass; with m == 1 or c_out_host == NULL they are not computed and c_out_host is not written.
+ * A thread owns j and j + m/2: it reads the four positions of a and of b that it alone writes or that nobody writes, so the
+ * update needs no second buffer.  x is inverted once on the host.  Two launches with the inner products, one without.
+ * ZKP_ERR_BAD_ARG: a NULL or misaligned a_dev / b_dev, n outside the rule, a and b overlapping, *x_host == 0 or >= r. */
+int32_t zkp_fr_ipa_fold_ab_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* a_dev, uint64_t* b_dev, size_t n, const uint64_t* x_host,
+                               uint64_t* c_out_host);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
