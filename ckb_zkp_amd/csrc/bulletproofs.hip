@@ -37,18 +37,6 @@ constexpr int SG = (int)BP_SUM_GROUP;
 constexpr int NT_COEFF = 9;                                      // t2 .. t10
 static_assert(NT_COEFF % SG == 0, "the sums are reduced in whole groups");
 
-// K Fr elements (Montgomery) as one kernel argument
-template <class F, int K>
-struct FrPack {
-  uint32_t v[K][F::N];
-  void set(int k, const void* host) { memcpy(v[k], host, 4 * F::N); }
-  __device__ __forceinline__ F get(int k) const {               // k a constant: scalar loads from the kernel argument segment
-    F x;
-#pragma unroll
-    for (int i = 0; i < F::N; i++) x.v[i] = v[k][i];
-    return x;
-  }
-};
 constexpr int JB = 17;                                           // bits of a thread's first index
 static_assert(((size_t)1 << JB) == (size_t)BP_THREADS * BP_MAX_GROUPS, "one table entry per bit of the largest thread index");
 // the scalars of the l(X), r(X) kernels; S_YB, S_ZB, S_QB: y^(2^b), z^(2^b), (z / y)^(2^b) for b < JB
@@ -61,7 +49,7 @@ struct BpVecs {
 };
 
 template <class P>
-__global__ __launch_bounds__(BT) void powers_kernel(FrPack<Fp<P>, P_COUNT> c, uint32_t* __restrict__ out, size_t n) {
+__global__ __launch_bounds__(BT) void powers_kernel(FrArgs<Fp<P>, P_COUNT> c, uint32_t* __restrict__ out, size_t n) {
   using F = Fp<P>;
   const size_t T = (size_t)gridDim.x * BT;
   const size_t j = (size_t)blockIdx.x * BT + threadIdx.x;
@@ -103,7 +91,7 @@ struct Coeffs {
 template <class F>
 struct Powers {
   F Y, Zp, U, yT, zT, qT;
-  __device__ __forceinline__ Powers(const FrPack<F, S_COUNT>& c, size_t j) {
+  __device__ __forceinline__ Powers(const FrArgs<F, S_COUNT>& c, size_t j) {
     Y = F::one();
     Zp = c.get(S_ZB);                                            // z^(j+1) = z z^j
     U = c.get(S_U0);
@@ -132,7 +120,7 @@ struct Powers {
 
 // partial[k * gridDim.x + block] = the block's share of t_(k+2)
 template <class P>
-__global__ __launch_bounds__(BT) void t_coeffs_kernel(BpVecs b, FrPack<Fp<P>, S_COUNT> c, uint32_t* __restrict__ partial) {
+__global__ __launch_bounds__(BT) void t_coeffs_kernel(BpVecs b, FrArgs<Fp<P>, S_COUNT> c, uint32_t* __restrict__ partial) {
   using F = Fp<P>;
   __shared__ __attribute__((aligned(16))) char smem[SG * BT * 32];
   const size_t T = (size_t)gridDim.x * BT;
@@ -172,7 +160,7 @@ __global__ __launch_bounds__(BT) void t_coeffs_kernel(BpVecs b, FrPack<Fp<P>, S_
 
 // l_x, r_x written for i < N; partial[block] = the block's share of <l_x, r_x>
 template <class P>
-__global__ __launch_bounds__(BT) void lr_eval_kernel(BpVecs b, FrPack<Fp<P>, S_COUNT> c, uint32_t* __restrict__ l_x,
+__global__ __launch_bounds__(BT) void lr_eval_kernel(BpVecs b, FrArgs<Fp<P>, S_COUNT> c, uint32_t* __restrict__ l_x,
                                                      uint32_t* __restrict__ r_x, uint32_t* __restrict__ partial) {
   using F = Fp<P>;
   __shared__ __attribute__((aligned(16))) char smem[BT * 32];
@@ -199,7 +187,7 @@ __global__ __launch_bounds__(BT) void lr_eval_kernel(BpVecs b, FrPack<Fp<P>, S_C
 // h = m / 2 pairs (h == 0: m == 1, the single element).  want_c: partial[block], partial[gridDim.x + block] = the block's
 // shares of cL and cR.
 template <class P>
-__global__ __launch_bounds__(BT) void fold_ab_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, size_t m, FrPack<Fp<P>, 2> c,
+__global__ __launch_bounds__(BT) void fold_ab_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, size_t m, FrArgs<Fp<P>, 2> c,
                                                      int want_c, uint32_t* __restrict__ partial) {
   using F = Fp<P>;
   __shared__ __attribute__((aligned(16))) char smem[2 * BT * 32];
@@ -236,19 +224,6 @@ __global__ __launch_bounds__(BT) void fold_ab_kernel(uint32_t* __restrict__ a, u
     acc[1].store(partial + ((size_t)gridDim.x + blockIdx.x) * 8);
   }
 }
-
-// out[k] = the sum of the nwg partials of sum k (one workgroup per sum)
-template <class P>
-__global__ __launch_bounds__(BT) void bp_final_kernel(const uint32_t* __restrict__ partial, uint32_t nwg, uint32_t* __restrict__ out) {
-  using F = Fp<P>;
-  __shared__ __attribute__((aligned(16))) char smem[BT * 32];
-  F acc[1] = {F::zero()};
-  for (uint32_t g = threadIdx.x; g < nwg; g += BT) acc[0] = acc[0] + F::load(partial + ((size_t)blockIdx.x * nwg + g) * 8);
-  fr_block_sum<F, BT, 1>(acc, smem);
-  if (threadIdx.x == 0) acc[0].store(out + (size_t)blockIdx.x * 8);
-}
-
-void require_curve(int curve) { ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE); }
 
 uint32_t groups_for(size_t n) { return (uint32_t)std::min<size_t>(std::max<size_t>((n + BT - 1) / BT, 1), BP_MAX_GROUPS); }
 
@@ -339,11 +314,6 @@ void set_bit_powers(Pack& c, int first, const Fr64& fr, Fr64::E base) {
   }
 }
 
-struct Span {
-  uintptr_t lo, hi;
-};
-bool disjoint(const Span& a, const Span& b) { return a.hi <= b.lo || b.hi <= a.lo; }
-
 // the rules of zkp_bp_vectors; returns the kernels' view of it
 BpVecs require_vectors(const zkp_bp_vectors* vecs) {
   ZKP_REQUIRE(vecs != nullptr, ZKP_ERR_BAD_ARG);
@@ -366,10 +336,10 @@ BpVecs require_vectors(const zkp_bp_vectors* vecs) {
 
 // y != 0, y and z below r; the scalars both l(X), r(X) kernels read, for T threads
 template <class F>
-FrPack<F, S_COUNT> lr_scalars(const Fr64& fr, const BpVecs& b, const uint64_t* y_host, const uint64_t* z_host, uint64_t T) {
+FrArgs<F, S_COUNT> lr_scalars(const Fr64& fr, const BpVecs& b, const uint64_t* y_host, const uint64_t* z_host, uint64_t T) {
   const Fr64::E y = Fr64::load(y_host), z = Fr64::load(z_host);
   const Fr64::E q = fr.mul(z, fr.inverse(y)), zn = fr.pow(z, b.n);
-  FrPack<F, S_COUNT> c{};
+  FrArgs<F, S_COUNT> c{};
   c.set(S_YT, fr.pow(y, T).data());
   c.set(S_ZT, fr.pow(z, T).data());
   c.set(S_QT, fr.pow(q, T).data());
@@ -391,7 +361,7 @@ void require_yz(int curve, const uint64_t* y_host, const uint64_t* z_host) {
 }  // namespace
 
 void fr_powers(zkp_ctx* ctx, int curve, const uint64_t* first_host, const uint64_t* ratio_host, uint64_t* out_dev, size_t n) {
-  require_curve(curve);
+  fr_require_curve(curve);
   if (n == 0) return;
   ZKP_REQUIRE(first_host && ratio_host && out_dev, ZKP_ERR_BAD_ARG);
   require_aligned16(out_dev);
@@ -404,7 +374,7 @@ void fr_powers(zkp_ctx* ctx, int curve, const uint64_t* first_host, const uint64
   hipStream_t st = ctx->cur->stream;
   with_fr(curve, [&](auto tag) {
     using P = decltype(tag);
-    FrPack<Fp<P>, P_COUNT> c{};
+    FrArgs<Fp<P>, P_COUNT> c{};
     c.set(P_FIRST, first_host);
     c.set(P_STEP, fr.pow(ratio, (uint64_t)nwg * BT).data());
     set_bit_powers(c, P_BITS, fr, ratio);
@@ -416,7 +386,7 @@ void fr_powers(zkp_ctx* ctx, int curve, const uint64_t* first_host, const uint64
 
 void fr_bp_t_coeffs(zkp_ctx* ctx, int curve, const zkp_bp_vectors* vecs, const uint64_t* y_host, const uint64_t* z_host,
                     uint64_t* t_out_host) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(t_out_host != nullptr, ZKP_ERR_BAD_ARG);
   const BpVecs b = require_vectors(vecs);
   require_yz(curve, y_host, z_host);
@@ -429,8 +399,7 @@ void fr_bp_t_coeffs(zkp_ctx* ctx, int curve, const zkp_bp_vectors* vecs, const u
     using P = decltype(tag);
     const auto c = lr_scalars<Fp<P>>(Fr64(curve), b, y_host, z_host, (uint64_t)nwg * BT);
     hipLaunchKernelGGL(t_coeffs_kernel<P>, dim3(nwg), dim3(BT), 0, st, b, c, sc.at<uint32_t>(o_part));
-    hipLaunchKernelGGL(bp_final_kernel<P>, dim3(NT_COEFF), dim3(BT), 0, st, (const uint32_t*)sc.at<uint32_t>(o_part), nwg,
-                       sc.at<uint32_t>(o_out));
+    fr_sum_partials<P, BT>(st, sc.at<uint32_t>(o_part), nwg, NT_COEFF, sc.at<uint32_t>(o_out));
   });
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipMemcpyAsync(t_out_host, sc.at<uint32_t>(o_out), NT_COEFF * 32, hipMemcpyDeviceToHost, st));
@@ -439,24 +408,16 @@ void fr_bp_t_coeffs(zkp_ctx* ctx, int curve, const zkp_bp_vectors* vecs, const u
 
 void fr_bp_lr_eval(zkp_ctx* ctx, int curve, const zkp_bp_vectors* vecs, const uint64_t* y_host, const uint64_t* z_host,
                    const uint64_t* x_host, uint64_t* l_x_dev, uint64_t* r_x_dev, uint64_t* t_x_out_host) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(x_host && l_x_dev && r_x_dev && t_x_out_host, ZKP_ERR_BAD_ARG);
   const BpVecs b = require_vectors(vecs);
   require_yz(curve, y_host, z_host);
   fr_require_canonical(curve, x_host, 1);
   require_aligned16(l_x_dev);
   require_aligned16(r_x_dev);
-  const Span lo{(uintptr_t)l_x_dev, (uintptr_t)l_x_dev + b.N * 32}, ro{(uintptr_t)r_x_dev, (uintptr_t)r_x_dev + b.N * 32};
-  ZKP_REQUIRE(disjoint(lo, ro), ZKP_ERR_BAD_ARG);
-  const struct {
-    const uint32_t* p;
-    size_t len;
-  } ins[7] = {{b.aL, b.n}, {b.aR, b.n}, {b.aO, b.n}, {b.w, b.n_w}, {b.v, b.n_w}, {b.sL, b.n_s}, {b.sR, b.n_s}};
-  for (const auto& e : ins) {
-    if (e.len == 0) continue;
-    const Span in{(uintptr_t)e.p, (uintptr_t)e.p + e.len * 32};
-    ZKP_REQUIRE(disjoint(lo, in) && disjoint(ro, in), ZKP_ERR_BAD_ARG);
-  }
+  require_disjoint_outputs({fr_span(l_x_dev, b.N, true), fr_span(r_x_dev, b.N, true), fr_span(b.aL, b.n, false),
+                            fr_span(b.aR, b.n, false), fr_span(b.aO, b.n, false), fr_span(b.w, b.n_w, false),
+                            fr_span(b.v, b.n_w, false), fr_span(b.sL, b.n_s, false), fr_span(b.sR, b.n_s, false)});   // length 0: never read
   const uint32_t nwg = groups_for(b.N);
   hipStream_t st = ctx->cur->stream;
   Scratch sc;
@@ -472,7 +433,7 @@ void fr_bp_lr_eval(zkp_ctx* ctx, int curve, const zkp_bp_vectors* vecs, const ui
     c.set(S_X5, fr.mul(fr.mul(x2, x2), x).data());
     hipLaunchKernelGGL(lr_eval_kernel<P>, dim3(nwg), dim3(BT), 0, st, b, c, reinterpret_cast<uint32_t*>(l_x_dev),
                        reinterpret_cast<uint32_t*>(r_x_dev), sc.at<uint32_t>(o_part));
-    hipLaunchKernelGGL(bp_final_kernel<P>, dim3(1), dim3(BT), 0, st, (const uint32_t*)sc.at<uint32_t>(o_part), nwg, sc.at<uint32_t>(o_out));
+    fr_sum_partials<P, BT>(st, sc.at<uint32_t>(o_part), nwg, 1, sc.at<uint32_t>(o_out));
   });
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipMemcpyAsync(t_x_out_host, sc.at<uint32_t>(o_out), 32, hipMemcpyDeviceToHost, st));
@@ -480,12 +441,12 @@ void fr_bp_lr_eval(zkp_ctx* ctx, int curve, const zkp_bp_vectors* vecs, const ui
 }
 
 void fr_ipa_fold_ab(zkp_ctx* ctx, int curve, uint64_t* a_dev, uint64_t* b_dev, size_t n, const uint64_t* x_host, uint64_t* c_out_host) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(a_dev && b_dev && x_host, ZKP_ERR_BAD_ARG);
   require_aligned16(a_dev);
   require_aligned16(b_dev);
   ZKP_REQUIRE(is_pow2(n) && n >= 2 && n <= ((size_t)1 << BP_MAX_LOG), ZKP_ERR_BAD_ARG);
-  ZKP_REQUIRE(disjoint({(uintptr_t)a_dev, (uintptr_t)a_dev + n * 32}, {(uintptr_t)b_dev, (uintptr_t)b_dev + n * 32}), ZKP_ERR_BAD_ARG);
+  require_disjoint_outputs({fr_span(a_dev, n, true), fr_span(b_dev, n, true)});
   fr_require_canonical(curve, x_host, 1);
   ZKP_REQUIRE(x_host[0] | x_host[1] | x_host[2] | x_host[3], ZKP_ERR_BAD_ARG);
   const size_t m = n / 2;
@@ -499,13 +460,12 @@ void fr_ipa_fold_ab(zkp_ctx* ctx, int curve, uint64_t* a_dev, uint64_t* b_dev, s
   uint32_t* d_part = want_c ? sc.at<uint32_t>(o_part) : nullptr;
   with_fr(curve, [&](auto tag) {
     using P = decltype(tag);
-    FrPack<Fp<P>, 2> c{};
+    FrArgs<Fp<P>, 2> c{};
     c.set(0, x_host);
     c.set(1, xi.data());
     hipLaunchKernelGGL(fold_ab_kernel<P>, dim3(nwg), dim3(BT), 0, st, reinterpret_cast<uint32_t*>(a_dev), reinterpret_cast<uint32_t*>(b_dev), m,
                        c, want_c ? 1 : 0, d_part);
-    if (want_c)
-      hipLaunchKernelGGL(bp_final_kernel<P>, dim3(2), dim3(BT), 0, st, (const uint32_t*)d_part, nwg, sc.at<uint32_t>(o_out));
+    if (want_c) fr_sum_partials<P, BT>(st, d_part, nwg, 2, sc.at<uint32_t>(o_out));
   });
   ZKP_HIP(hipGetLastError());
   if (want_c) ZKP_HIP(hipMemcpyAsync(c_out_host, sc.at<uint32_t>(o_out), 2 * 32, hipMemcpyDeviceToHost, st));

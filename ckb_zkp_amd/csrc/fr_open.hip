@@ -30,19 +30,6 @@ constexpr int EG = (int)FR_OPEN_EVAL_GROUP;
 constexpr int LT = (int)FR_OPEN_LINCOMB_THREADS;
 constexpr int MAXP = (int)FR_OPEN_MAX_POLYS;
 
-// K Fr elements (Montgomery) as one kernel argument
-template <class F, int K>
-struct FrArgs {
-  uint32_t v[K][F::N];
-  void set(int k, const void* host) { memcpy(v[k], host, 4 * F::N); }
-  __device__ __forceinline__ F get(int k) const {            // k uniform: scalar loads from the kernel argument segment
-    F x;
-#pragma unroll
-    for (int i = 0; i < F::N; i++) x.v[i] = v[k][i];
-    return x;
-  }
-};
-
 // the vectors of a call: unused entries are NULL with length 0
 struct OpenTable {
   const uint32_t* p[MAXP];
@@ -87,17 +74,6 @@ __global__ __launch_bounds__(ET) void eval_many_kernel(OpenTable tb, uint32_t co
   }
 }
 
-// out[k] = the sum of polynomial k's nwg partials (one workgroup per polynomial)
-template <class P>
-__global__ __launch_bounds__(ET) void eval_final_kernel(const uint32_t* __restrict__ partial, uint32_t nwg, uint32_t* __restrict__ out) {
-  using F = Fp<P>;
-  __shared__ __attribute__((aligned(16))) char smem[ET * 32];
-  F acc[1] = {F::zero()};
-  for (uint32_t b = threadIdx.x; b < nwg; b += ET) acc[0] = acc[0] + F::load(partial + ((size_t)blockIdx.x * nwg + b) * 8);
-  fr_block_sum<F, ET, 1>(acc, smem);
-  if (threadIdx.x == 0) acc[0].store(out + (size_t)blockIdx.x * 8);
-}
-
 // out[i] = sum_{k < count, i < n[k]} c_k p_k[i]; every term has n[k] >= 1 and c_k != 0 (the host dropped the others)
 template <class P>
 __global__ __launch_bounds__(LT) void lincomb_kernel(OpenTable tb, uint32_t count, FrArgs<Fp<P>, MAXP> c, uint32_t* out, size_t n_out) {
@@ -109,8 +85,6 @@ __global__ __launch_bounds__(LT) void lincomb_kernel(OpenTable tb, uint32_t coun
     if (i < tb.n[k]) acc = acc + c.get(k) * F::load(tb.p[k] + i * 8);
   acc.store(out + i * 8);
 }
-
-void require_curve(int curve) { ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE); }
 
 // the rules both entries share; returns the longest length
 size_t require_table(size_t count, const uint64_t* const* p_dev, const size_t* ns) {
@@ -127,20 +101,11 @@ size_t require_table(size_t count, const uint64_t* const* p_dev, const size_t* n
   return nmax;
 }
 
-hostf::FrE host_pow(const hostf::HostField& fr, hostf::FrE a, uint64_t e) {
-  hostf::FrE r = fr.one_();
-  for (; e; e >>= 1) {
-    if (e & 1) r = fr.mul(r, a);
-    a = fr.mul(a, a);
-  }
-  return r;
-}
-
 }  // namespace
 
 void fr_poly_eval_many(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* p_dev, const size_t* ns, const uint64_t* z_host,
                        uint64_t* out_host) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(z_host && out_host, ZKP_ERR_BAD_ARG);
   const size_t nmax = require_table(count, p_dev, ns);
   fr_require_canonical(curve, z_host, 1);
@@ -151,9 +116,7 @@ void fr_poly_eval_many(zkp_ctx* ctx, int curve, size_t count, const uint64_t* co
   }
   const uint32_t nwg = (uint32_t)std::min<size_t>(std::max<size_t>((nmax + ET - 1) / ET, 1), FR_OPEN_EVAL_MAX_BLOCKS);
   const hostf::HostField fr = hostf::fr_field(curve);
-  hostf::FrE z{};
-  memcpy(z.data(), z_host, 32);
-  const hostf::FrE zT = host_pow(fr, z, (uint64_t)nwg * ET);
+  const hostf::FrE z = fr_host_load(z_host), zT = fr.pow(z, (uint64_t)nwg * ET);
   hipStream_t st = ctx->cur->stream;
   Scratch sc;
   const size_t o_out = sc.take(count * 32), o_part = sc.take(count * (size_t)nwg * 32);
@@ -161,11 +124,10 @@ void fr_poly_eval_many(zkp_ctx* ctx, int curve, size_t count, const uint64_t* co
   with_fr(curve, [&](auto tag) {
     using P = decltype(tag);
     FrArgs<Fp<P>, 2> c;
-    c.set(0, z.data());
-    c.set(1, zT.data());
+    c.set(0, z);
+    c.set(1, zT);
     hipLaunchKernelGGL(eval_many_kernel<P>, dim3(nwg), dim3(ET), 0, st, tb, (uint32_t)count, c, sc.at<uint32_t>(o_part));
-    hipLaunchKernelGGL(eval_final_kernel<P>, dim3((unsigned)count), dim3(ET), 0, st, (const uint32_t*)sc.at<uint32_t>(o_part), nwg,
-                       sc.at<uint32_t>(o_out));
+    fr_sum_partials<P, ET>(st, sc.at<uint32_t>(o_part), nwg, (uint32_t)count, sc.at<uint32_t>(o_out));
   });
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipMemcpyAsync(out_host, sc.at<uint32_t>(o_out), count * 32, hipMemcpyDeviceToHost, st));
@@ -174,16 +136,14 @@ void fr_poly_eval_many(zkp_ctx* ctx, int curve, size_t count, const uint64_t* co
 
 void fr_lincomb(zkp_ctx* ctx, int curve, size_t count, const uint64_t* const* p_dev, const size_t* ns, const uint64_t* coeffs_host,
                 uint64_t* out_dev, size_t n_out) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(coeffs_host && out_dev, ZKP_ERR_BAD_ARG);
   const size_t nmax = require_table(count, p_dev, ns);
   ZKP_REQUIRE(n_out >= 1 && n_out <= ((size_t)1 << FR_OPEN_MAX_LOG) && nmax <= n_out, ZKP_ERR_BAD_ARG);
   require_aligned16(out_dev);
-  const uintptr_t o = (uintptr_t)out_dev;
   for (size_t k = 0; k < count; k++) {
     if (ns[k] == 0) continue;
-    const uintptr_t a = (uintptr_t)p_dev[k];
-    ZKP_REQUIRE(a == o || a + ns[k] * 32 <= o || o + n_out * 32 <= a, ZKP_ERR_BAD_ARG);   // the same vector or disjoint ones
+    ZKP_REQUIRE(same_or_disjoint((uintptr_t)p_dev[k], ns[k] * 32, (uintptr_t)out_dev, n_out * 32), ZKP_ERR_BAD_ARG);
   }
   fr_require_canonical(curve, coeffs_host, count);
   hipStream_t st = ctx->cur->stream;

@@ -222,23 +222,6 @@ __global__ __launch_bounds__(GKR_THREADS) void gkr_bind_kernel(GkrPtrs tb, size_
   (lo + x * (F::load(t + (j + m) * 8) - lo)).store(t + j * 8);
 }
 
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + GKR_THREADS - 1) / GKR_THREADS); }
-
-struct Span {
-  uintptr_t lo, hi;
-  bool out;
-};
-// outputs overlap nothing; inputs may overlap each other (the rule of spark.hip)
-void require_disjoint_outputs(std::vector<Span> spans) {
-  std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.lo != b.lo ? a.lo < b.lo : a.out > b.out; });
-  uintptr_t end_any = 0, end_out = 0;
-  for (const Span& sp : spans) {
-    ZKP_REQUIRE(sp.lo >= (sp.out ? end_any : end_out), ZKP_ERR_BAD_ARG);
-    end_any = std::max(end_any, sp.hi);
-    if (sp.out) end_out = std::max(end_out, sp.hi);
-  }
-}
-
 template <class T>
 T* upload_array(zkp_gkr_layer* layer, const std::vector<T>& host) {
   if (host.empty()) return nullptr;
@@ -257,7 +240,7 @@ void tables_t(zkp_ctx* ctx, const zkp_gkr_layer* layer, const uint32_t* G, const
   hipStream_t st = ctx->cur->stream;
   // the scratch first: growing it frees and allocates, which would come between the launches
   uint32_t* partial = sd.n_long ? ctx->poly_tmp.as<uint32_t>((size_t)sd.n_chunks * NP * 8) : nullptr;
-  hipLaunchKernelGGL((gkr_tables_kernel<P, PHASE>), dim3(blocks_for(nodes)), dim3(GKR_THREADS), 0, st, sd.ptr, sd.ent, nodes, G, w, out);
+  hipLaunchKernelGGL((gkr_tables_kernel<P, PHASE>), dim3(fr_blocks(nodes, GKR_THREADS)), dim3(GKR_THREADS), 0, st, sd.ptr, sd.ent, nodes, G, w, out);
   if (sd.n_long) {
     hipLaunchKernelGGL((gkr_chunk_kernel<P, PHASE>), dim3(sd.n_chunks), dim3(GKR_THREADS), 0, st, sd.chunks, sd.ent, G, w, partial);
     hipLaunchKernelGGL((gkr_long_kernel<P, PHASE>), dim3(sd.n_long), dim3(GKR_THREADS), 0, st, sd.longs, partial, out);
@@ -274,13 +257,13 @@ void round_t(zkp_ctx* ctx, const GkrPtrs& tb, size_t len, const uint64_t* fu_hos
   const FrArg<F> xa(bind_host);
   if (!evals_out_host) {                                         // bind only
     const size_t m = len / 2;
-    hipLaunchKernelGGL(gkr_bind_kernel<P>, dim3(blocks_for(m), NT), dim3(GKR_THREADS), 0, st, tb, m, xa);
+    hipLaunchKernelGGL(gkr_bind_kernel<P>, dim3(fr_blocks(m, GKR_THREADS), NT), dim3(GKR_THREADS), 0, st, tb, m, xa);
     ZKP_HIP(hipGetLastError());
     ZKP_HIP(hipStreamSynchronize(st));
     return;
   }
   const size_t h = bind_host ? len / 4 : len / 2;
-  const uint32_t nwg = blocks_for(h);
+  const uint32_t nwg = fr_blocks(h, GKR_THREADS);
   Scratch sc;                                                    // one partial per (sum, workgroup): at most 4 * 2^19 elements
   const size_t o_part = sc.take((size_t)NS * nwg * 32), o_out = sc.take(2 * 32);
   sc.resolve(ctx->poly_tmp);
@@ -371,16 +354,16 @@ void gkr_layer_info(const zkp_gkr_layer* layer, uint64_t info[8]) {
 }
 
 void fr_gkr_eval_layer(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, const uint64_t* in_dev, uint64_t* out_dev) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   require_layer(ctx, layer);
   ZKP_REQUIRE(in_dev && out_dev, ZKP_ERR_BAD_ARG);
   require_aligned16(in_dev);
   require_aligned16(out_dev);
   const size_t total = (size_t)1 << layer->log_out, nodes = (size_t)1 << layer->log_in;
-  require_disjoint_outputs({{(uintptr_t)in_dev, (uintptr_t)in_dev + nodes * 32, false}, {(uintptr_t)out_dev, (uintptr_t)out_dev + total * 32, true}});
+  require_disjoint_outputs({fr_span(in_dev, nodes, false), fr_span(out_dev, total, true)});
   hipStream_t st = ctx->cur->stream;
   with_fr(curve, [&](auto tag) {
-    hipLaunchKernelGGL(gkr_eval_kernel<decltype(tag)>, dim3(blocks_for(total)), dim3(GKR_THREADS), 0, st, layer->nat, (size_t)layer->n_gates,
+    hipLaunchKernelGGL(gkr_eval_kernel<decltype(tag)>, dim3(fr_blocks(total, GKR_THREADS)), dim3(GKR_THREADS), 0, st, layer->nat, (size_t)layer->n_gates,
                        total, reinterpret_cast<const uint32_t*>(in_dev), reinterpret_cast<uint32_t*>(out_dev));
   });
   ZKP_HIP(hipGetLastError());
@@ -389,7 +372,7 @@ void fr_gkr_eval_layer(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, cons
 
 void fr_gkr_tables(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, int phase, const uint64_t* g_dev, const uint64_t* w_dev,
                    uint64_t* const* out_dev) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   require_layer(ctx, layer);
   ZKP_REQUIRE(phase == 1 || phase == 2, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(g_dev && w_dev && out_dev, ZKP_ERR_BAD_ARG);
@@ -398,12 +381,12 @@ void fr_gkr_tables(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, int phas
   const size_t total = (size_t)1 << layer->log_out, nodes = (size_t)1 << layer->log_in;
   const int np = gkr_tables_of(phase);
   ZKP_REQUIRE(phase == 1 || out_dev[2] == nullptr, ZKP_ERR_BAD_ARG);
-  std::vector<Span> spans = {{(uintptr_t)g_dev, (uintptr_t)g_dev + total * 32, false}, {(uintptr_t)w_dev, (uintptr_t)w_dev + nodes * 32, false}};
+  std::vector<MemSpan> spans = {fr_span(g_dev, total, false), fr_span(w_dev, nodes, false)};
   GkrPtrs out{};
   for (int p = 0; p < np; p++) {
     ZKP_REQUIRE(out_dev[p] != nullptr, ZKP_ERR_BAD_ARG);
     require_aligned16(out_dev[p]);
-    spans.push_back({(uintptr_t)out_dev[p], (uintptr_t)out_dev[p] + nodes * 32, true});
+    spans.push_back(fr_span(out_dev[p], nodes, true));
     out.t[p] = reinterpret_cast<uint32_t*>(out_dev[p]);
   }
   require_disjoint_outputs(spans);
@@ -417,7 +400,7 @@ void fr_gkr_tables(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, int phas
 
 void fr_gkr_round(zkp_ctx* ctx, int curve, int phase, uint64_t* const* tables_dev, size_t len, const uint64_t* fu_host,
                   const uint64_t* bind_host, uint64_t* evals_out_host) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   ZKP_REQUIRE(phase == 1 || phase == 2, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(tables_dev != nullptr, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(bind_host || evals_out_host, ZKP_ERR_BAD_ARG);

@@ -128,6 +128,14 @@ struct HostField {
     for (int i = 0; i < k; i++) a = mul(a, a);
     return a;
   }
+  E pow(E a, uint64_t e) const {
+    E r = one_();
+    for (; e; e >>= 1) {
+      if (e & 1) r = mul(r, a);
+      a = mul(a, a);
+    }
+    return r;
+  }
   E inverse(const E& a) const {                        // Fermat: a^(p-2)
     E r = one_();
     for (int bit = 32 * N - 1; bit >= 0; bit--) {

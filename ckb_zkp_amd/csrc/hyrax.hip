@@ -141,39 +141,6 @@ __global__ __launch_bounds__(HT) void hyrax_round_kernel(const uint32_t* __restr
   }
 }
 
-// one workgroup per point: out[p] = the sum of its nwg partials
-template <class P>
-__global__ __launch_bounds__(HT) void hyrax_final_kernel(const uint32_t* __restrict__ partial, uint32_t nwg, uint32_t* __restrict__ out) {
-  using F = Fp<P>;
-  __shared__ __attribute__((aligned(16))) char smem[HT * 32];
-  F acc[1] = {F::zero()};
-  for (uint32_t c = threadIdx.x; c < nwg; c += HT) acc[0] = acc[0] + F::load(partial + ((size_t)blockIdx.x * nwg + c) * 8);
-  fr_block_sum<F, HT, 1>(acc, smem);
-  if (threadIdx.x == 0) acc[0].store(out + (size_t)blockIdx.x * 8);
-}
-
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + HT - 1) / HT); }
-inline int log2_of(size_t pow2) {
-  int l = 0;
-  while (((size_t)1 << l) < pow2) l++;
-  return l;
-}
-
-struct Span {
-  uintptr_t lo, hi;
-  bool out;
-};
-// outputs overlap nothing; inputs may overlap each other (the rule of gkr.hip)
-void require_disjoint_outputs(std::vector<Span> spans) {
-  std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.lo != b.lo ? a.lo < b.lo : a.out > b.out; });
-  uintptr_t end_any = 0, end_out = 0;
-  for (const Span& sp : spans) {
-    ZKP_REQUIRE(sp.lo >= (sp.out ? end_any : end_out), ZKP_ERR_BAD_ARG);
-    end_any = std::max(end_any, sp.hi);
-    if (sp.out) end_out = std::max(end_out, sp.hi);
-  }
-}
-
 void require_layer(zkp_ctx* ctx, const zkp_gkr_layer* layer) {
   ZKP_REQUIRE(layer != nullptr, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(layer->device == ctx->device, ZKP_ERR_BAD_HANDLE);
@@ -186,7 +153,7 @@ void round_t(zkp_ctx* ctx, const zkp_gkr_layer* layer, uint32_t* v, uint32_t* eq
   hipStream_t st = ctx->cur->stream;
   const size_t rows = (size_t)1 << layer->log_in;
   const size_t h = (bind_host ? len / 2 : len) / 2;               // the columns of the evaluation
-  const uint32_t gx = blocks_for(h), gy = (uint32_t)((layer->n_gates + HYRAX_CHUNK - 1) / HYRAX_CHUNK), nwg = gx * gy;
+  const uint32_t gx = fr_blocks(h, HT), gy = (uint32_t)((layer->n_gates + HYRAX_CHUNK - 1) / HYRAX_CHUNK), nwg = gx * gy;
   uint32_t *d_part = nullptr, *d_out = nullptr;
   if (evals_out_host) {                                            // the scratch first: growing it frees and allocates
     Scratch sc;                                                    // one partial per (point, workgroup): at most 3 * 2^20 elements
@@ -197,14 +164,14 @@ void round_t(zkp_ctx* ctx, const zkp_gkr_layer* layer, uint32_t* v, uint32_t* eq
   }
   if (bind_host) {
     const size_t m = len / 2;
-    hipLaunchKernelGGL(hyrax_bind_kernel<P>, dim3(blocks_for((rows + 1) * m)), dim3(HT), 0, st, v, eq, rows, log_n, log2_of(m),
+    hipLaunchKernelGGL(hyrax_bind_kernel<P>, dim3(fr_blocks((rows + 1) * m, HT)), dim3(HT), 0, st, v, eq, rows, log_n, log2_ceil(m),
                        FrArg<F>(bind_host), finals);
   }
   if (evals_out_host) {
     const GkrSide& sd = layer->side[0];
     hipLaunchKernelGGL(hyrax_round_kernel<P>, dim3(nwg), dim3(HT), 0, st, sd.ptr, sd.ent, (uint32_t)layer->n_gates, (uint32_t)rows, v, eq, w,
                        log_n, h, gx, d_part);
-    hipLaunchKernelGGL(hyrax_final_kernel<P>, dim3(3), dim3(HT), 0, st, d_part, nwg, d_out);
+    fr_sum_partials<P, HT>(st, d_part, nwg, 3, d_out);
   }
   ZKP_HIP(hipGetLastError());
   if (evals_out_host) ZKP_HIP(hipMemcpyAsync(evals_out_host, d_out, 3 * 32, hipMemcpyDeviceToHost, st));
@@ -214,19 +181,19 @@ void round_t(zkp_ctx* ctx, const zkp_gkr_layer* layer, uint32_t* v, uint32_t* eq
 }  // namespace
 
 void fr_gkr_eval_layer_batch(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, const uint64_t* in_dev, uint64_t* out_dev, size_t n) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   require_layer(ctx, layer);
   ZKP_REQUIRE(in_dev && out_dev, ZKP_ERR_BAD_ARG);
   require_aligned16(in_dev);
   require_aligned16(out_dev);
   ZKP_REQUIRE(is_pow2(n) && n <= ((size_t)1 << HYRAX_MAX_LOG), ZKP_ERR_BAD_ARG);
-  const int log_n = log2_of(n);
+  const int log_n = log2_ceil(n);
   ZKP_REQUIRE((int)layer->log_in + log_n <= HYRAX_MAX_LOG && (int)layer->log_out + log_n <= HYRAX_MAX_LOG, ZKP_ERR_BAD_ARG);
   const size_t total = ((size_t)1 << layer->log_out) * n, below = ((size_t)1 << layer->log_in) * n;
-  require_disjoint_outputs({{(uintptr_t)in_dev, (uintptr_t)in_dev + below * 32, false}, {(uintptr_t)out_dev, (uintptr_t)out_dev + total * 32, true}});
+  require_disjoint_outputs({fr_span(in_dev, below, false), fr_span(out_dev, total, true)});
   hipStream_t st = ctx->cur->stream;
   with_fr(curve, [&](auto tag) {
-    hipLaunchKernelGGL(hyrax_eval_kernel<decltype(tag)>, dim3(blocks_for(total)), dim3(HT), 0, st, layer->nat, (size_t)layer->n_gates, total,
+    hipLaunchKernelGGL(hyrax_eval_kernel<decltype(tag)>, dim3(fr_blocks(total, HT)), dim3(HT), 0, st, layer->nat, (size_t)layer->n_gates, total,
                        log_n, reinterpret_cast<const uint32_t*>(in_dev), reinterpret_cast<uint32_t*>(out_dev));
   });
   ZKP_HIP(hipGetLastError());
@@ -235,7 +202,7 @@ void fr_gkr_eval_layer_batch(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer
 
 void fr_gkr_dp_round(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, uint64_t* v_dev, uint64_t* eq_dev, const uint64_t* w_dev,
                      size_t n, size_t len, const uint64_t* bind_host, uint64_t* evals_out_host, uint64_t* finals_dev) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   require_layer(ctx, layer);
   ZKP_REQUIRE(v_dev && eq_dev && w_dev, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(bind_host || evals_out_host, ZKP_ERR_BAD_ARG);
@@ -244,7 +211,7 @@ void fr_gkr_dp_round(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, uint64
   require_aligned16(w_dev);
   require_aligned16(finals_dev);
   ZKP_REQUIRE(is_pow2(n) && is_pow2(len) && len <= n && n <= ((size_t)1 << HYRAX_MAX_LOG), ZKP_ERR_BAD_ARG);
-  const int log_n = log2_of(n);
+  const int log_n = log2_ceil(n);
   ZKP_REQUIRE((int)layer->log_in + log_n <= HYRAX_MAX_LOG, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(!bind_host || len >= 2, ZKP_ERR_BAD_ARG);
   const size_t after = bind_host ? len / 2 : len;
@@ -256,10 +223,8 @@ void fr_gkr_dp_round(zkp_ctx* ctx, int curve, const zkp_gkr_layer* layer, uint64
   }
   if (bind_host) fr_require_canonical(curve, bind_host, 1);
   const size_t rows = (size_t)1 << layer->log_in, total = (size_t)1 << layer->log_out;
-  std::vector<Span> spans = {{(uintptr_t)v_dev, (uintptr_t)v_dev + rows * n * 32, true},
-                             {(uintptr_t)eq_dev, (uintptr_t)eq_dev + n * 32, true},
-                             {(uintptr_t)w_dev, (uintptr_t)w_dev + total * 32, false}};
-  if (finals_dev) spans.push_back({(uintptr_t)finals_dev, (uintptr_t)finals_dev + rows * 32, true});
+  std::vector<MemSpan> spans = {fr_span(v_dev, rows * n, true), fr_span(eq_dev, n, true), fr_span(w_dev, total, false)};
+  if (finals_dev) spans.push_back(fr_span(finals_dev, rows, true));
   require_disjoint_outputs(spans);
   with_fr(curve, [&](auto tag) {
     round_t<decltype(tag)>(ctx, layer, reinterpret_cast<uint32_t*>(v_dev), reinterpret_cast<uint32_t*>(eq_dev),

@@ -32,19 +32,6 @@ constexpr int ST = (int)PLONK_SCAN_THREADS;
 constexpr int SI = (int)PLONK_SCAN_ITEMS;
 constexpr int QT = (int)PLONK_QUOT_THREADS;
 
-// K Fr elements (Montgomery) as one kernel argument
-template <class F, int K>
-struct FrArgs {
-  uint32_t v[K][F::N];
-  void set(int k, const hostf::FrE& e) { memcpy(v[k], e.data(), 4 * F::N); }
-  __device__ __forceinline__ F get(int k) const {            // k: a compile-time constant at every call site
-    F x;
-#pragma unroll
-    for (int i = 0; i < F::N; i++) x.v[i] = v[k][i];
-    return x;
-  }
-};
-
 template <class F>
 __device__ __forceinline__ F fr_select(bool c, const F& a, const F& b) {
   F r;
@@ -232,12 +219,6 @@ __global__ __launch_bounds__(QT) void quotient_kernel(QuotPtrs p, size_t N, size
   }
 }
 
-hostf::FrE host_load(const uint64_t* host) {
-  hostf::FrE e{};
-  memcpy(e.data(), host, 32);
-  return e;
-}
-
 int fr_two_adicity(int curve) { return curve == ZKP_BN254 ? hostf::consts::Bn254Fr::TWO_ADICITY : hostf::consts::Bls381Fr::TWO_ADICITY; }
 
 // the generator of the domain of size 2^log that zkp_ntt_dev uses (ntt.hip ntt_setup_kernel), and the coset generator
@@ -252,14 +233,6 @@ hostf::FrE host_coset_gen(int curve) {
   return e;
 }
 
-int log2_of(size_t v) {
-  int l = 0;
-  while (((size_t)1 << l) < v) l++;
-  return l;
-}
-
-void require_curve(int curve) { ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE); }
-
 // the rules every PLONK call shares: n = 2^log_n rows with log_n >= 2, and a domain of 4n points
 void require_plonk_domain(int curve, uint32_t log_n) {
   ZKP_REQUIRE(log_n >= 2, ZKP_ERR_BAD_ARG);
@@ -272,13 +245,12 @@ size_t row_threads(size_t n) { return std::min(n, (size_t)PLONK_QUOT_THREADS * P
 }  // namespace
 
 void fr_prefix_product(zkp_ctx* ctx, int curve, const uint64_t* in_dev, uint64_t* out_dev, size_t n, uint64_t* total_out_host) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(in_dev && out_dev, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(n >= 1 && n <= ((size_t)1 << PLONK_SCAN_MAX_LOG), ZKP_ERR_BAD_ARG);
   require_aligned16(in_dev);
   require_aligned16(out_dev);
-  const uintptr_t a = (uintptr_t)in_dev, b = (uintptr_t)out_dev;
-  ZKP_REQUIRE(a == b || a + n * 32 <= b || b + n * 32 <= a, ZKP_ERR_BAD_ARG);   // the same vector or disjoint ones
+  ZKP_REQUIRE(same_or_disjoint((uintptr_t)in_dev, n * 32, (uintptr_t)out_dev, n * 32), ZKP_ERR_BAD_ARG);
   hipStream_t st = ctx->cur->stream;
   Scratch sc;
   const size_t o_tot = sc.take(32), o_lv = sc.take(scan_scratch_elems(n) * 32);
@@ -296,7 +268,7 @@ void fr_prefix_product(zkp_ctx* ctx, int curve, const uint64_t* in_dev, uint64_t
 void fr_plonk_perm_z(zkp_ctx* ctx, int curve, const uint64_t* const* w_dev, const uint64_t* const* sigma_dev, uint32_t log_n,
                      const uint64_t* ks_host, const uint64_t* beta_host, const uint64_t* gamma_host, uint64_t* z_out_dev,
                      int32_t* closes_out_host) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(w_dev && sigma_dev && ks_host && beta_host && gamma_host && z_out_dev && closes_out_host, ZKP_ERR_BAD_ARG);
   PermPtrs pp{};
   for (int s = 0; s < 4; s++) {
@@ -313,7 +285,7 @@ void fr_plonk_perm_z(zkp_ctx* ctx, int curve, const uint64_t* const* w_dev, cons
   fr_require_canonical(curve, gamma_host, 1);
   const size_t n = (size_t)1 << log_n, T = row_threads(n);
   const hostf::HostField fr = hostf::fr_field(curve);
-  const hostf::FrE beta = host_load(beta_host), w = host_root(fr, curve, (int)log_n);
+  const hostf::FrE beta = fr_host_load(beta_host), w = host_root(fr, curve, (int)log_n);
   hipStream_t st = ctx->cur->stream;
   Scratch sc;                                                    // z_out is written last, from scratch only: it may be an input
   const size_t o_tot = sc.take(32), o_num = sc.take(n * 32), o_den = sc.take(n * 32), o_lv = sc.take(scan_scratch_elems(n) * 32);
@@ -324,12 +296,12 @@ void fr_plonk_perm_z(zkp_ctx* ctx, int curve, const uint64_t* const* w_dev, cons
     using P = decltype(tag);
     using F = Fp<P>;
     FrArgs<F, PZ_COUNT> c;
-    for (int s = 0; s < 4; s++) c.set(PZ_KB + s, fr.mul(host_load(ks_host + 4 * s), beta));
+    for (int s = 0; s < 4; s++) c.set(PZ_KB + s, fr.mul(fr_host_load(ks_host + 4 * s), beta));
     c.set(PZ_BETA, beta);
-    c.set(PZ_GAMMA, host_load(gamma_host));
+    c.set(PZ_GAMMA, fr_host_load(gamma_host));
     c.set(PZ_W, w);
-    c.set(PZ_WT, fr.pow2k(w, log2_of(T)));
-    hipLaunchKernelGGL(perm_terms_kernel<P>, dim3((unsigned)((T + QT - 1) / QT)), dim3(QT), 0, st, pp, n, T, c, num, den);
+    c.set(PZ_WT, fr.pow2k(w, log2_ceil(T)));
+    hipLaunchKernelGGL(perm_terms_kernel<P>, dim3(fr_blocks(T, QT)), dim3(QT), 0, st, pp, n, T, c, num, den);
   });
   ZKP_HIP(hipGetLastError());
   fr_batch_inverse(ctx, curve, reinterpret_cast<uint64_t*>(den), n);
@@ -349,7 +321,7 @@ void fr_plonk_quotient(zkp_ctx* ctx, int curve, const uint64_t* const* w_4n, con
                        const uint64_t* const* q_4n, const uint64_t* const* sigma_4n, const uint64_t* l1_4n, uint32_t log_n,
                        const uint64_t* ks_host, const uint64_t* beta_host, const uint64_t* gamma_host, const uint64_t* alpha_host,
                        uint64_t* t_out_dev) {
-  require_curve(curve);
+  fr_require_curve(curve);
   ZKP_REQUIRE(w_4n && z_4n && pi_4n && q_4n && sigma_4n && l1_4n && t_out_dev, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(ks_host && beta_host && gamma_host && alpha_host, ZKP_ERR_BAD_ARG);
   require_plonk_domain(curve, log_n);
@@ -365,13 +337,13 @@ void fr_plonk_quotient(zkp_ctx* ctx, int curve, const uint64_t* const* w_4n, con
   in[16] = pi_4n;
   in[17] = l1_4n;
   require_aligned16(t_out_dev);
-  const uintptr_t o = (uintptr_t)t_out_dev;
+  std::vector<MemSpan> spans = {fr_span(t_out_dev, N, true)};    // point i + 4 of z is read after point i is written
   for (int k = 0; k < 18; k++) {
     ZKP_REQUIRE(in[k] != nullptr, ZKP_ERR_BAD_ARG);
     require_aligned16(in[k]);
-    const uintptr_t a = (uintptr_t)in[k];
-    ZKP_REQUIRE(a + N * 32 <= o || o + N * 32 <= a, ZKP_ERR_BAD_ARG);       // point i + 4 of z is read after point i is written
+    spans.push_back(fr_span(in[k], N, false));
   }
+  require_disjoint_outputs(std::move(spans));
   for (int s = 0; s < 4; s++) {
     qp.w[s] = reinterpret_cast<const uint32_t*>(w_4n[s]);
     qp.s[s] = reinterpret_cast<const uint32_t*>(sigma_4n[s]);
@@ -385,7 +357,7 @@ void fr_plonk_quotient(zkp_ctx* ctx, int curve, const uint64_t* const* w_4n, con
   fr_require_canonical(curve, gamma_host, 1);
   fr_require_canonical(curve, alpha_host, 1);
   const hostf::HostField fr = hostf::fr_field(curve);
-  const hostf::FrE beta = host_load(beta_host), alpha = host_load(alpha_host);
+  const hostf::FrE beta = fr_host_load(beta_host), alpha = fr_host_load(alpha_host);
   const hostf::FrE w = host_root(fr, curve, (int)log_n + 2), g = host_coset_gen(curve);
   // v_4n_inversed (ahp/indexer/mod.rs:223-225): x_i^n - 1 = g^n (w^n)^i - 1 takes four values
   const hostf::FrE iota = fr.pow2k(w, (int)log_n);
@@ -395,9 +367,9 @@ void fr_plonk_quotient(zkp_ctx* ctx, int curve, const uint64_t* const* w_4n, con
     using P = decltype(tag);
     using F = Fp<P>;
     FrArgs<F, QC_COUNT> c;
-    for (int s = 0; s < 4; s++) c.set(QC_KB + s, fr.mul(host_load(ks_host + 4 * s), beta));
+    for (int s = 0; s < 4; s++) c.set(QC_KB + s, fr.mul(fr_host_load(ks_host + 4 * s), beta));
     c.set(QC_BETA, beta);
-    c.set(QC_GAMMA, host_load(gamma_host));
+    c.set(QC_GAMMA, fr_host_load(gamma_host));
     c.set(QC_ALPHA, alpha);
     c.set(QC_ALPHA2, fr.mul(alpha, alpha));
     for (int k = 0; k < 4; k++) {
@@ -406,8 +378,8 @@ void fr_plonk_quotient(zkp_ctx* ctx, int curve, const uint64_t* const* w_4n, con
     }
     c.set(QC_G, g);
     c.set(QC_W, w);
-    c.set(QC_WT, fr.pow2k(w, log2_of(T)));
-    hipLaunchKernelGGL(quotient_kernel<P>, dim3((unsigned)((T + QT - 1) / QT)), dim3(QT), 0, st, qp, N, T, c,
+    c.set(QC_WT, fr.pow2k(w, log2_ceil(T)));
+    hipLaunchKernelGGL(quotient_kernel<P>, dim3(fr_blocks(T, QT)), dim3(QT), 0, st, qp, N, T, c,
                        reinterpret_cast<uint32_t*>(t_out_dev));
   });
   ZKP_HIP(hipGetLastError());

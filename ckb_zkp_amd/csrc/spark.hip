@@ -195,15 +195,14 @@ void circuits_t(zkp_ctx* ctx, const std::vector<SpGroup>& groups, size_t count, 
   if (hash) ZKP_HIP(hipMemcpyAsync(d_groups, groups.data(), groups.size() * sizeof(SpGroup), hipMemcpyHostToDevice, st));
   ZKP_HIP(hipMemcpyAsync(d_circ, circuits, count * sizeof(uint32_t*), hipMemcpyHostToDevice, st));
 
-  int log_n = 0;
-  while (((size_t)1 << log_n) < n) log_n++;
+  const int log_n = log2_ceil(n);
   // strided passes down to 2^SP_TAIL_LOG elements: radix 8 first (the longest layers), the remainder (radix 2 or 4) last
   uint32_t l = 0;
   for (int rem = log_n - SP_TAIL_LOG; rem > 0;) {
     const int rl = std::min(rem, 3);
     const size_t s = (n >> l) >> rl;
     const bool h = hash && l == 0;
-    const dim3 grid((unsigned)((s + SP_THREADS - 1) / SP_THREADS), (unsigned)(h ? groups.size() : count));
+    const dim3 grid(fr_blocks(s, SP_THREADS), (unsigned)(h ? groups.size() : count));
     if (h) launch_pass<P, true>(st, rl, grid, d_groups, d_circ, n, l, k);
     else launch_pass<P, false>(st, rl, grid, d_groups, d_circ, n, l, k);
     l += rl;
@@ -218,18 +217,13 @@ void circuits_t(zkp_ctx* ctx, const std::vector<SpGroup>& groups, size_t count, 
   ZKP_HIP(hipStreamSynchronize(st));
 }
 
-struct Span {
-  uintptr_t lo, hi;
-  bool circuit;
-};
-
 }  // namespace
 
 void fr_spark_circuits(zkp_ctx* ctx, int curve, size_t count, const uint32_t* const* addr_dev, const uint64_t* const* val_dev,
                        const uint32_t* const* ts_dev, const uint32_t* ts_add, uint64_t* const* circuits_dev, size_t n,
                        const uint64_t* gamma1_host, const uint64_t* gamma2_host, uint64_t* roots_host) {
   const bool hash = val_dev != nullptr;
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   ZKP_REQUIRE(count >= 1 && count <= SP_MAX_CIRCUITS, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(is_pow2(n) && n >= 2 && n <= ((size_t)1 << SP_MAX_LOG), ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(circuits_dev && roots_host, ZKP_ERR_BAD_ARG);
@@ -239,12 +233,11 @@ void fr_spark_circuits(zkp_ctx* ctx, int curve, size_t count, const uint32_t* co
     ZKP_REQUIRE(addr_dev && ts_dev && ts_add && gamma1_host && gamma2_host, ZKP_ERR_BAD_ARG);
     fr_require_canonical(curve, gamma1_host, 1);
     fr_require_canonical(curve, gamma2_host, 1);
-    memcpy(g1.data(), gamma1_host, 32);
-    memcpy(g2.data(), gamma2_host, 32);
+    g1 = fr_host_load(gamma1_host);
+    g2 = fr_host_load(gamma2_host);
   }
-  // circuit buffers overlap nothing; inputs may overlap each other (shared between entries).  Sorted by start, a circuit must begin
-  // at or after the end of everything before it, an input at or after the end of every circuit before it.
-  std::vector<Span> spans;
+  // circuit buffers overlap nothing; inputs may overlap each other (shared between entries)
+  std::vector<MemSpan> spans;
   spans.reserve(count * (hash ? 4 : 1));
   for (size_t i = 0; i < count; i++) {
     const uintptr_t c = (uintptr_t)circuits_dev[i];
@@ -259,13 +252,7 @@ void fr_spark_circuits(zkp_ctx* ctx, int curve, size_t count, const uint32_t* co
     if (a) spans.push_back({a, a + n * 4, false});
     if (t) spans.push_back({t, t + n * 4, false});
   }
-  std::sort(spans.begin(), spans.end(), [](const Span& x, const Span& y) { return x.lo < y.lo; });
-  uintptr_t end_any = 0, end_circ = 0;
-  for (const Span& sp : spans) {
-    ZKP_REQUIRE(sp.lo >= (sp.circuit ? end_any : end_circ), ZKP_ERR_BAD_ARG);
-    end_any = std::max(end_any, sp.hi);
-    if (sp.circuit) end_circ = std::max(end_circ, sp.hi);
-  }
+  require_disjoint_outputs(std::move(spans));
 
   // groups: entries with the same (addr, val, ts) and different ts_add share one hash
   std::vector<SpGroup> groups;

@@ -11,7 +11,7 @@
 // slots of one term) share is bound by the first slot that reaches it in the thread's own order; the later ones read the two bound
 // values back (same thread, same addresses: program order).  Terms are spread over grid.y by groups that share no table.
 //
-// Reduction: fr_block_sum (fr_dev.hpp) leaves one partial per (workgroup, term, point); sc_final_kernel (one workgroup per
+// Reduction: fr_block_sum (fr_dev.hpp) leaves one partial per (workgroup, term, point); fr_sum_partials (one workgroup per
 // (term, point)) adds them.  No hand-off between workgroups of one launch.  Field addition is exact: the order does not matter.
 //
 // Without a bind (round 0) the same kernel runs with one thread per j < len/2; a bind without evaluation (after the last round)
@@ -103,18 +103,6 @@ __global__ __launch_bounds__(SC_THREADS) void sc_round_kernel(const ScTerm* term
   }
 }
 
-// out[o] = sum of the nwg partials of output o (one workgroup per output)
-template <class P>
-__global__ __launch_bounds__(SC_THREADS) void sc_final_kernel(const uint32_t* __restrict__ partial, uint32_t nwg,
-                                                              uint32_t* __restrict__ out) {
-  using F = Fp<P>;
-  __shared__ __attribute__((aligned(16))) char smem[SC_THREADS * 32];
-  F acc[1] = {F::zero()};
-  for (uint32_t c = threadIdx.x; c < nwg; c += SC_THREADS) acc[0] = acc[0] + F::load(partial + ((size_t)blockIdx.x * nwg + c) * 8);
-  fr_block_sum<F, SC_THREADS, 1>(acc, smem);
-  if (threadIdx.x == 0) acc[0].store(out + (size_t)blockIdx.x * 8);
-}
-
 // t[j] = t[j] + x (t[j + m] - t[j]) for j < m, table blockIdx.y
 template <class P>
 __global__ __launch_bounds__(SC_THREADS) void sc_bind_kernel(uint32_t* const* __restrict__ tables, size_t m, FrArg<Fp<P>> xa) {
@@ -185,7 +173,7 @@ void round_t(zkp_ctx* ctx, int kind, size_t count, uint64_t* const* tables, size
     const size_t m = len / 2;
     uint32_t** d_tab = reinterpret_cast<uint32_t**>(ctx->poly_tmp.get(uniq.size() * sizeof(uint32_t*)));
     ZKP_HIP(hipMemcpyAsync(d_tab, uniq.data(), uniq.size() * sizeof(uint32_t*), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sc_bind_kernel<P>, dim3((unsigned)((m + SC_THREADS - 1) / SC_THREADS), (unsigned)uniq.size()), dim3(SC_THREADS),
+    hipLaunchKernelGGL(sc_bind_kernel<P>, dim3(fr_blocks(m, SC_THREADS), (unsigned)uniq.size()), dim3(SC_THREADS),
                        0, st, d_tab, m, FrArg<Fp<P>>(bind_host));
     ZKP_HIP(hipGetLastError());
     ZKP_HIP(hipStreamSynchronize(st));
@@ -227,7 +215,7 @@ void round_t(zkp_ctx* ctx, int kind, size_t count, uint64_t* const* tables, size
   }
 
   const size_t h = bind_host ? len / 4 : len / 2;
-  const uint32_t nwg = (uint32_t)((h + SC_THREADS - 1) / SC_THREADS);
+  const uint32_t nwg = fr_blocks(h, SC_THREADS);
   const size_t nout = count * np;
   // one partial per (workgroup, term, point): count * points * len / 16 (len / 32 with a bind) bytes, e.g. 6 MB for one fused
   // phase-one term of 2^26 rows.  Many terms over very long tables (256 terms of 2^28 rows: 13 GB) end as ZKP_ERR_OOM, as zkp_accel.h says.
@@ -246,7 +234,7 @@ void round_t(zkp_ctx* ctx, int kind, size_t count, uint64_t* const* tables, size
   if (kind == ZKP_SC_EQ_AB_MINUS_C) launch_round<P, ZKP_SC_EQ_AB_MINUS_C>(st, bind_host != nullptr, grid, d_terms, d_groups, h, bind_host, d_part);
   else if (kind == ZKP_SC_PROD2) launch_round<P, ZKP_SC_PROD2>(st, bind_host != nullptr, grid, d_terms, d_groups, h, bind_host, d_part);
   else launch_round<P, ZKP_SC_PROD3>(st, bind_host != nullptr, grid, d_terms, d_groups, h, bind_host, d_part);
-  hipLaunchKernelGGL(sc_final_kernel<P>, dim3((unsigned)nout), dim3(SC_THREADS), 0, st, d_part, nwg, d_out);
+  fr_sum_partials<P, SC_THREADS>(st, d_part, nwg, (uint32_t)nout, d_out);
   ZKP_HIP(hipGetLastError());
   ZKP_HIP(hipMemcpyAsync(evals_out_host, d_out, nout * 32, hipMemcpyDeviceToHost, st));
   ZKP_HIP(hipStreamSynchronize(st));
@@ -259,7 +247,7 @@ void eq_t(zkp_ctx* ctx, const uint64_t* r_host, size_t k, uint32_t* out) {
   if (k) ZKP_HIP(hipMemcpyAsync(rd, r_host, k * 32, hipMemcpyHostToDevice, st));
   if (k >= SC_EQ_LOW) {
     const size_t threads = (size_t)1 << (k - SC_EQ_LOW);
-    hipLaunchKernelGGL((sc_eq_kernel<P, SC_EQ_LOW>), dim3((unsigned)((threads + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st,
+    hipLaunchKernelGGL((sc_eq_kernel<P, SC_EQ_LOW>), dim3(fr_blocks(threads, SC_THREADS)), dim3(SC_THREADS), 0, st,
                        rd, (uint32_t)k, threads, out);
   } else {
     hipLaunchKernelGGL((sc_eq_kernel<P, 0>), dim3(1), dim3(SC_THREADS), 0, st, rd, (uint32_t)k, (size_t)1 << k, out);
@@ -272,7 +260,7 @@ void eq_t(zkp_ctx* ctx, const uint64_t* r_host, size_t k, uint32_t* out) {
 
 void fr_sumcheck_round(zkp_ctx* ctx, int curve, int kind, size_t count, uint64_t* const* tables, size_t len, const uint64_t* bind_host,
                        uint64_t* evals_out_host) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   ZKP_REQUIRE(kind == ZKP_SC_EQ_AB_MINUS_C || kind == ZKP_SC_PROD2 || kind == ZKP_SC_PROD3, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(bind_host || evals_out_host, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(count <= SC_MAX_TERMS, ZKP_ERR_BAD_ARG);
@@ -286,7 +274,7 @@ void fr_sumcheck_round(zkp_ctx* ctx, int curve, int kind, size_t count, uint64_t
 }
 
 void fr_eq_evals(zkp_ctx* ctx, int curve, const uint64_t* r_host, size_t k, uint64_t* out_dev) {
-  ZKP_REQUIRE(curve == ZKP_BN254 || curve == ZKP_BLS12_381, ZKP_ERR_UNSUPPORTED_CURVE);
+  fr_require_curve(curve);
   ZKP_REQUIRE(k <= (size_t)SC_MAX_LOG, ZKP_ERR_BAD_ARG);
   ZKP_REQUIRE(out_dev && (k == 0 || r_host), ZKP_ERR_BAD_ARG);
   require_aligned16(out_dev);

@@ -205,6 +205,8 @@ def test_lr_argument_rules(ctx):
         for p, ln in zip(inp.ptrs, inp.lens):                                            # an output over an input
             assert lr_call(inp.vecs, good, good, good, p + 32 * (ln - 1), ro) == -1
             assert lr_call(inp.vecs, good, good, good, lo, p - 32 * (N - 1)) == -1
+            assert lr_call(inp.vecs, good, good, good, p - 32, ro) == -1                 # the input nested inside the output
+            assert lr_call(inp.vecs, good, good, good, lo, p - 32) == -1
         assert (t_out == SENT).all() and (tx_out == SENT).all()
         assert np.array_equal(out.read(), out.expected(c, [None, None]))
         assert inp.unchanged()

@@ -277,7 +277,7 @@ def quick(ctx):
     print(json.dumps(dict(case="quick", log_n=10,
                           calls=["powers: 1 launch", "t_coeffs: 2 launches", "lr_eval: 2 launches", "fold_ab with cL, cR: 2 launches",
                                  "fold_ab without: 1 launch"],
-                          expected_kernel_calls=dict(powers_kernel=1, t_coeffs_kernel=1, lr_eval_kernel=1, fold_ab_kernel=2, bp_final_kernel=3))),
+                          expected_kernel_calls=dict(powers_kernel=1, t_coeffs_kernel=1, lr_eval_kernel=1, fold_ab_kernel=2, fr_sum_partials_kernel=3))),
           flush=True)
 
 

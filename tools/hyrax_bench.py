@@ -290,7 +290,7 @@ def quick(ctx):
     print(json.dumps(dict(case="quick", shape=dict(log_gates=log_g, log_copies=10),
                           calls=["eval_layer_batch: 1 launch", "round 0, evaluate: 2 launches", "bind + evaluate: 3 launches",
                                  "closing call, bind + finals: 1 launch"],
-                          expected_kernel_calls=dict(hyrax_eval_kernel=1, hyrax_round_kernel=2, hyrax_final_kernel=2, hyrax_bind_kernel=2))),
+                          expected_kernel_calls=dict(hyrax_eval_kernel=1, hyrax_round_kernel=2, fr_sum_partials_kernel=2, hyrax_bind_kernel=2))),
           flush=True)
 
 
