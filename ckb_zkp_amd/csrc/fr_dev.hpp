@@ -1,7 +1,8 @@
-// The helpers that Fr-only units (poly.hip, sumcheck.hip, spark.hip, gkr.hip, plonk.hip, fr_open.hip, hyrax.hip, bulletproofs.hip)
-// share: one Fr element (FrArg) or K of them (FrArgs) as a kernel argument, the workgroup sum (fr_block_sum), the sum of every
-// workgroup's partials (fr_sum_partials), the curve dispatch (with_fr), the argument rules with the aliasing rule of mem_spans.hpp
-// among them, the carving of one scratch allocation (Scratch) and the layout of ctx->poly_consts (PolyConsts).
+// The helpers that Fr-only units (poly.hip, sumcheck.hip, spark.hip, gkr.hip, plonk.hip, fr_open.hip, hyrax.hip, bulletproofs.hip;
+// marlin.hip, which has no kernels, for the host-side rules) share: one Fr element (FrArg) or K of them (FrArgs) as a kernel
+// argument, the workgroup sum (fr_block_sum), the sum of every workgroup's partials (fr_sum_partials), the curve dispatch
+// (with_fr), the argument rules with the aliasing rule of mem_spans.hpp among them, the carving of one scratch allocation
+// (Scratch) and the layout of ctx->poly_consts (PolyConsts).
 // Header only: no translation unit, no exported symbol.  A new Fr-only unit starts from here.
 #pragma once
 #include <cstring>

@@ -358,3 +358,98 @@ def test_native_marlin_prover_matches_oracle(ctx, curve, samples, swap):
         nidx.free()
         ck.powers_of_g.free()
         ck.powers_of_gamma_g.free()
+
+
+# ---- the A/B arms of csrc/marlin.hip (csrc/tune.hpp): "same proof bytes" on either arm of every switch
+MARLIN_ARMS = {
+    "default": {},
+    "early_off": {"ZKP_MARLIN_EARLY": 0},
+    "early_fft": {"ZKP_MARLIN_EARLY_FFT": 1},
+    "device_affine": {"ZKP_MARLIN_HOST_AFFINE": 0},
+    "early_eval": {"ZKP_MARLIN_EARLY_EVAL": 1},
+    "all_flipped": {"ZKP_MARLIN_EARLY": 0, "ZKP_MARLIN_EARLY_FFT": 1, "ZKP_MARLIN_HOST_AFFINE": 0, "ZKP_MARLIN_EARLY_EVAL": 1},
+}
+ARMS_BETA_SRS = 0x13579BDF2468ACE
+# zkp_marlin_timing's work counters of one proof of mimc_chain_instance(curve, 2, seed=91): |H| = 32, |K| = 64, |B| = 256, SRS
+# degree 189, the same on both curves.  MEASURED on the commit BEFORE marlin_prove was split into rounds (this test ran there
+# first), never taken from the restructured code: the restructuring must reproduce them.  No arm changes any of them: an early MSM
+# counts the points the round's batch would have counted, and the first round's early transforms (ZKP_MARLIN_EARLY_FFT) replace
+# the second round's one for one because both rounds choose the same product domain.  One query point (gamma == beta) halves
+# open_points: one witness MSM over the SRS instead of two.
+ARMS_COUNTERS = {
+    "two_points": dict(commit_points=667, open_points=378, ntt_count=16, ntt_elements=1537),
+    "one_point": dict(commit_points=667, open_points=189, ntt_count=16, ntt_elements=1537),
+}
+_arms_oracle_cache = {}
+
+
+def _arms_oracle(curve):
+    """The instance and the oracle's three proofs of it (supplied messages, derived messages, gamma == beta): computed once per
+    curve on the CPU, shared by every arm, never modified."""
+    if curve not in _arms_oracle_cache:
+        from ckb_zkp_amd.circuits import mimc_chain_instance
+        c = get_curve(curve)
+        inst = mimc_chain_instance(curve, 2, seed=91)
+        ocirc = og.MimcChain(OC[curve], inst.constants, inst.preimages)
+        oidx = om.index(OC[curve], ocirc)
+        assert (oidx["dh"].size, oidx["dk"].size, oidx["db"].size, oidx["max_degree"]) == (32, 64, 256, 189)
+        pp = okzg.setup(OC[curve], oidx["max_degree"], ARMS_BETA_SRS)
+        ic = om.index_commitments(oidx, pp)
+        R, ch = _rand_inputs(c, oidx["dh"].size, seed=57)
+        ch_one = dict(ch, gamma=ch["beta"])
+        o_fixed = om.create_proof(oidx, pp, ocirc, R, ch)
+        o_random = om.create_random_proof(oidx, pp, ic, ocirc, R)
+        o_one = om.create_proof(oidx, pp, ocirc, R, ch_one)
+        assert len(o_fixed["opening_proofs"]) == 2 and len(o_random["opening_proofs"]) == 2
+        assert len(o_one["opening_proofs"]) == 1 and len(o_one["query"]) == 21
+        assert om.verify_proof(oidx, pp, ic, o_one, inst.z[1:inst.num_inputs], ch_one)
+        _arms_oracle_cache[curve] = dict(inst=inst, oidx=oidx, pp=pp, ic=ic, ivk=om.index_verifier_key(oidx, pp, ic), R=R, ch=ch,
+                                         ch_one=ch_one, fixed=o_fixed, random=o_random, one=o_one)
+    return _arms_oracle_cache[curve]
+
+
+@pytest.mark.parametrize("curve,arm", [("bn254", a) for a in MARLIN_ARMS] + [("bls12_381", "default"), ("bls12_381", "all_flipped")])
+def test_native_marlin_arms_give_the_oracle_proof(ctx, monkeypatch, curve, arm):
+    """Either arm of ZKP_MARLIN_EARLY / _EARLY_FFT / _HOST_AFFINE / _EARLY_EVAL, one at a time and all together, each latched by a
+    context of its own: zkp_marlin_prove gives the oracle's proof for supplied messages, for derived messages (which the oracle's
+    verifier accepts) and for gamma == beta (ONE query point: 21 queries, one opening proof — the path no other test runs), and
+    does the work the default arms do, by the counters of zkp_marlin_timing."""
+    from ckb_zkp_amd import marlin as marlin_native
+    from tests.util import variant_ctx
+    o = _arms_oracle(curve)
+    inst, oidx, pp, ic = o["inst"], o["oidx"], o["pp"], o["ic"]
+    x, w = inst.z[:inst.num_inputs], inst.z[inst.num_inputs:]
+    with variant_ctx(monkeypatch, ctx.device, {}, MARLIN_ARMS[arm]) as v:
+        nidx = marlin_native.NativeIndex(v, inst)
+        ck = kzg10.setup(v, curve, nidx.max_degree, ARMS_BETA_SRS)
+        try:
+            assert (nidx.hs, nidx.ks, nidx.bs, nidx.max_degree) == (32, 64, 256, 189)
+            runs = [("fixed", None, o["ch"], "two_points"), ("random", o["ivk"], None, "two_points"),
+                    ("one", None, o["ch_one"], "one_point")]
+            for kind, ivk, ch, counters in runs:
+                p, want = marlin_native.prove_native(v, nidx, ck, ivk, x, w, o["R"], ch), o[kind]
+                print(curve, arm, kind, {k: p["timing"][k] for k in ARMS_COUNTERS[counters]})
+                assert p["commitments"] == want["commitments"], kind                   # the shifted commitments ride in the pairs
+                assert p["challenges"] == want["challenges"], kind
+                assert p["query"] == want["query"] and p["evaluations"] == want["evaluations"], kind
+                assert p["opening_proofs"] == want["opening_proofs"], kind
+                assert len(p["opening_proofs"]) == (1 if kind == "one" else 2)
+                if kind == "random":
+                    wire = dict(commitments=p["commitments"], evaluations=p["evaluations"], opening_proofs=p["opening_proofs"])
+                    assert om.verify_random_proof(oidx, pp, ic, wire, x[1:])
+                assert {k: p["timing"][k] for k in ARMS_COUNTERS[counters]} == ARMS_COUNTERS[counters], kind
+        finally:
+            nidx.free()
+            ck.powers_of_g.free()
+            ck.powers_of_gamma_g.free()
+
+
+def test_marlin_index_upload_rejects_an_unknown_curve(ctx):
+    """the curve is checked before anything of the descriptor is read: ZKP_ERR_UNSUPPORTED_CURVE (-2), nothing returned"""
+    import ctypes as C
+    from ckb_zkp_amd import _lib
+    d = _lib.MarlinIndexDesc()
+    d.curve, d.num_inputs, d.n = 7, 1, 4
+    h = C.c_void_p()
+    assert ctx.lib.zkp_marlin_index_upload(ctx.h, C.byref(d), C.byref(h)) == -2
+    assert not h.value

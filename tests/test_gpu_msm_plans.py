@@ -16,6 +16,7 @@ zkp_ctx_config and by the internal switches of csrc/tune.hpp.  Each case below i
 Expectations are (sum d_i k_i mod r) G in Python integers and the oracle's group law; the default plan's result on the same input
 is compared as an extra.  Nothing starts a process."""
 import contextlib
+import functools
 import random
 import re
 
@@ -23,19 +24,15 @@ import numpy as np
 import pytest
 
 from ckb_zkp_amd import codec
-from ckb_zkp_amd.api import Context
 from ckb_zkp_amd.params import get_curve
 from oracle.pyref.curves import Group
 from tests import msm_plan_ref as M
+from tests import util
 from tests.util import OC, jac_limbs_to_affine_oracle, random_points, to_abi_points
 
 pytestmark = pytest.mark.gpu
 CFG = [("bn254", 1), ("bn254", 2), ("bls12_381", 1), ("bls12_381", 2)]
 G1 = [("bn254", 1), ("bls12_381", 1)]
-# every switch of the table (csrc/tune.hpp ZKP_TUNE_ROWS; tests/test_msm_plan_ref.py holds the list against the table test's own, on
-# the CPU) and the defaults of the public fields (capi.hip): none may leak into a variant
-TUNE_NAMES = M.tune_switch_names()
-CFG_NAMES = ["ZKP_MSM_C", "ZKP_MSM_C_G2", "ZKP_MSM_CHUNK", "ZKP_TABLE_BUDGET_GB"]
 PLAN_RE = re.compile(r"\[msm\] bases group=(\d+) n=(\d+): c=(\d+) W=(\d+) wide=(\d+) k=(\d+) copies=(\d+)")
 N_EDGE, N_MULTI = 48, 2 * 2048 + 513
 EDGE_CASES = [(48, 0), (1, 0), (0, 0), (17, 5), (60, 0), (3, 47)]            # (scalars, offset): 60 overruns the bases, (3, 47) leaves one
@@ -45,25 +42,8 @@ N_BOUNDS = 14                                                                 # 
 
 @pytest.fixture
 def variant_ctx(monkeypatch):
-    """variant_ctx(device, config, env): a context created under `env` (internal switches) with `config` (public fields).  Every
-    switch of the table is deleted first, `env` is gone again before the caller sees the context; closed on exit."""
-    @contextlib.contextmanager
-    def make(device, config, env):
-        assert set(env) <= set(TUNE_NAMES), env
-        for name in TUNE_NAMES + CFG_NAMES:
-            monkeypatch.delenv(name, raising=False)
-        for name, value in env.items():
-            monkeypatch.setenv(name, str(value))
-        try:
-            v = Context(device, dict(config) or None)
-        finally:
-            for name in env:
-                monkeypatch.delenv(name, raising=False)
-        try:
-            yield v
-        finally:
-            v.close()
-    return make
+    """variant_ctx(device, config, env): tests.util.variant_ctx on this test's monkeypatch"""
+    return functools.partial(util.variant_ctx, monkeypatch)
 
 
 class Inputs:

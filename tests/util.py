@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests: oracle <-> ABI conversions."""
+import contextlib
 import random
 
 import numpy as np
@@ -13,6 +14,33 @@ OC = {"bn254": ofields.BN254, "bls12_381": ofields.BLS12_381}
 # smaller representative each — same code paths, a quarter of the points — for a suite that has to fit a time limit.  Default: full.
 import os
 TEST_FULL = os.environ.get("ZKP_TEST_FULL", "1") != "0"
+
+
+CFG_NAMES = ["ZKP_MSM_C", "ZKP_MSM_C_G2", "ZKP_MSM_CHUNK", "ZKP_TABLE_BUDGET_GB"]   # the public fields' defaults (capi.hip)
+
+
+@contextlib.contextmanager
+def variant_ctx(monkeypatch, device, config, env):
+    """A context created under `env` (internal switches of csrc/tune.hpp) with `config` (public fields).  Every switch of the table
+    and every default of the public fields is deleted first (none may leak into a variant), `env` is gone again before the caller
+    sees the context; closed on exit."""
+    from ckb_zkp_amd.api import Context
+    from tests.msm_plan_ref import tune_switch_names
+    tune_names = tune_switch_names()
+    assert set(env) <= set(tune_names), env
+    for name in tune_names + CFG_NAMES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, str(value))
+    try:
+        v = Context(device, dict(config) or None)
+    finally:
+        for name in env:
+            monkeypatch.delenv(name, raising=False)
+    try:
+        yield v
+    finally:
+        v.close()
 
 
 def jac_to_affine(ctx, curve, group, xyz):
