@@ -1,5 +1,5 @@
 """Builds tests/hip/*.hip into tests/hip/build/libzkp_field_probe.so and runs it: a test-only probe that puts every primitive of
-the device arithmetic (field_dev.hpp, unsat_dev.hpp, bucket_dev.hpp, coop_dev.hpp) behind its own one-lane-per-case kernel.
+the device arithmetic (field_dev.hpp, unsat_dev.hpp, bucket_dev.hpp, coop_dev.hpp, ec_dev.hpp) behind its own one-lane-per-case kernel.
 
 The product headers are included unchanged and compiled with the flags of ckb_zkp_amd/build.py (FLAGS + UNROLL, default macros).
 ZKP_PROBE_CSRC=<dir> takes the headers from another directory and builds into build/<ZKP_PROBE_TAG or "alt">/ (sensitivity runs
@@ -41,6 +41,13 @@ for _c in (0, 1):
     for _p in (0, 1):
         UNITS.append(("probe_g2.hip", f"probe_g2_c{_c}_p{_p}.o",
                       [f"-DPROBE_CURVE={_c}", f"-DPROBE_G2_PART={_p}", f"-DPROBE_G2_ENTRY=probe_g2_c{_c}_p{_p}"]))
+# ec_dev.hpp: one object per curve x group x part, the multiplier inlined where the product's msm_group unit inlines it (build.py)
+for _c in (0, 1):
+    for _g in (1, 2):
+        for _p in range(4):
+            UNITS.append(("probe_ec.hip", f"probe_ec_c{_c}_g{_g}_p{_p}.o",
+                          [f"-DPROBE_CURVE={_c}", f"-DPROBE_GROUP={_g}", f"-DPROBE_EC_PART={_p}", f"-DPROBE_EC_ENTRY=probe_ec_c{_c}_g{_g}_p{_p}"]
+                          + (["-DZKP_INLINE_MUL"] if (_c, _g) != (1, 2) else [])))
 
 
 def _deps():

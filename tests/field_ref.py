@@ -1,6 +1,7 @@
 """Exact reference and edge-case generator for the device arithmetic probe (tests/field_probe.py, tests/hip/).
 
 Everything here is Python integer arithmetic: no device code, no oracle library; oracle/pyref only for the affine group law.
+The saturated point arithmetic of ec_dev.hpp (EcOp) is checked against that group law alone.
 
 An unsaturated element (unsat_dev.hpp) is L limbs of B bits; limbs 0..L-2 are < 2^B when "normalised", the top limb carries the
 rest.  A value is not "an element below p" but "an integer below K*p"; the generator below puts operands at the top of the range
@@ -1081,6 +1082,203 @@ class BkDblMemOp(BkDblOp):
     MEM = True
 
 
+# ------------------------------------------------------------------------------------------------------------ ec_dev.hpp
+class EcOp(PointOp):
+    """XYZZ<F> of ec_dev.hpp on canonical saturated Montgomery words, one method per operation.  The reference is the affine group
+    law of oracle/pyref in Python integers; a result is compared as a GROUP ELEMENT (x / zz, y / zzz after normalising here), every
+    stored coordinate must be canonical (below p) and every non-identity result must keep zz^3 == zzz^2.  The identity is zz == 0.
+    ctx = (case class, expected affine point or None, extra)."""
+    KINDS = ("dbl_affine", "dbl", "madd", "madd_fast", "add", "to_affine", "store_jacobian", "from_jacobian")
+
+    def __init__(self, kind, g, fields=BASE_FIELDS):
+        super().__init__(kind, g, fields)
+        self.base = kind.split("_", 1)[1]
+        assert self.base in self.KINDS
+
+    def W(self, F):
+        return self.g * F.N
+
+    def nout(self, F):
+        W = self.W(F)
+        return {"to_affine": 2 * W, "store_jacobian": 3 * W, "madd_fast": 4 * W + 1}.get(self.base, 4 * W)
+
+    # ---- words <-> field elements
+    def enc(self, F, *elts):
+        return flat(*[F.words(ci * F.R % F.p) for c in elts for ci in self.PL(F).comps(c)])
+
+    def dec(self, F, row, n, tag):
+        PL, W = self.PL(F), self.W(F)
+        out = []
+        for k in range(n):
+            raw = [F.from_words(row[k * W + i * F.N:k * W + (i + 1) * F.N]) for i in range(self.g)]
+            assert all(v < F.p for v in raw), f"{tag}: coordinate {k} is not canonical: {[hex(v) for v in raw]}"
+            out.append(PL.elt([v * F.r_inv % F.p for v in raw]))
+        return out
+
+    def xyzz(self, F, P, z):
+        """(x z^2, y z^3, z^2, z^3) as field elements."""
+        Fo = self.PL(F).G.F
+        z2 = Fo.sqr(z)
+        z3 = Fo.mul(z2, z)
+        return [Fo.mul(P[0], z2), Fo.mul(P[1], z3), z2, z3]
+
+    def identities(self, F, rng):
+        """The forms of the identity: inf() = (1, 1, 0, 0), all zero, and zz == 0 beside ARBITRARY x, y, zzz."""
+        PL, Fo = self.PL(F), self.PL(F).G.F
+        return [[Fo.one, Fo.one, Fo.zero, Fo.zero], [Fo.zero] * 4, [PL.rand_elt(rng), PL.rand_elt(rng), Fo.zero, PL.rand_elt(rng)],
+                [PL.elt([F.p - 1] * self.g), Fo.zero, Fo.zero, Fo.one]]
+
+    def zs(self, F, rng, n):
+        """Z values: 1, p - 1, and random ones (never 0)."""
+        PL, Fo = self.PL(F), self.PL(F).G.F
+        return [Fo.one, PL.elt([F.p - 1] + [0] * (self.g - 1)), PL.elt([F.p - 1] * self.g)] + [PL.rand_elt(rng) for _ in range(n)]
+
+    def points(self, F, rng, n=28):
+        """The patterned points of the layer, the curve points with x in {0, 1, p - 1} (and u, 1 + u over Fq2) that exist — they
+        need not lie in the prime-order subgroup, the formulas do not know it — and a chain of sums for variety."""
+        PL, G, Fo = self.PL(F), self.PL(F).G, self.PL(F).G.F
+        pts = PL.affine_points(rng, nrand=2)
+        xs = [Fo.zero, Fo.one, Fo.neg(Fo.one)] + ([(0, 1), (1, 1), (0, F.p - 1)] if self.g == 2 else [])
+        special = [P for P in (PL.point_from_x(x) for x in xs) if P is not None]
+        assert all(G.on_curve(P) for P in special)
+        Q = pts[1]
+        chain = []
+        while len(chain) < n:
+            Q = G.add(Q, pts[2])
+            chain.append(Q)
+        return special + [G.neg(P) for P in special] + pts + chain, len(special)
+
+    def cases(self, F, rng):
+        PL, G, Fo = self.PL(F), self.PL(F).G, self.PL(F).G.F
+        pts, nspecial = self.points(F, rng)
+        ids = self.identities(F, rng)
+        b = self.base
+        out = []
+
+        def put(kind, words, want, extra=None):
+            out.append((words, None, (kind, want, extra)))
+
+        def other(i):                                       # a point with another x
+            Q = pts[(7 * i + 3) % len(pts)]
+            return Q if Q[0] != pts[i][0] else G.add(Q, PL.G.gen)
+        if b == "dbl_affine":
+            for P in pts:
+                put("generic", self.enc(F, *P), G.add(P, P))
+            for P in pts[:8]:
+                put("y = 0", self.enc(F, P[0], Fo.zero), None)
+            put("identity", self.enc(F, Fo.zero, Fo.zero), None)
+            for _ in range(120):
+                P = G.add(pts[rng.randrange(len(pts))], pts[rng.randrange(len(pts))])
+                if P is not None:
+                    put("generic", self.enc(F, *P), G.add(P, P))
+        elif b == "dbl":
+            for i, P in enumerate(pts):
+                for z in self.zs(F, rng, 3):
+                    put("generic", self.enc(F, *self.xyzz(F, P, z)), G.add(P, P))
+            for P in pts[:8]:
+                c = self.xyzz(F, P, PL.rand_elt(rng))
+                put("y = 0", self.enc(F, c[0], Fo.zero, c[2], c[3]), None)
+            for I in ids:
+                put("identity", self.enc(F, *I), None)
+        elif b in ("madd", "madd_fast"):
+            fast = b == "madd_fast"
+            for i, P in enumerate(pts):
+                Q = other(i)
+                for z in self.zs(F, rng, 2):
+                    a = self.enc(F, *self.xyzz(F, P, z))
+                    put("generic", a + self.enc(F, *Q), G.add(P, Q), (True, a))
+                    put("addend identity", a + self.enc(F, Fo.zero, Fo.zero), P, (True, a))
+                    # P + P with the accumulator under another Z: xyzz_dbl_affine_slow; madd_fast declines
+                    put("P + P", a + self.enc(F, *P), G.add(P, P), (not fast, a))
+                    put("P + (-P)", a + self.enc(F, *G.neg(P)), None, (not fast, a))
+                for I in ids[:3]:
+                    a = self.enc(F, *I)
+                    put("acc identity", a + self.enc(F, *P), P, (True, a))
+            for I in ids:
+                a = self.enc(F, *I)
+                put("identity + identity", a + self.enc(F, Fo.zero, Fo.zero), None, (True, a))
+        elif b == "add":
+            for i, P in enumerate(pts):
+                Q = other(i)
+                zs = self.zs(F, rng, 3)
+                for t, z in enumerate(zs):
+                    a = self.enc(F, *self.xyzz(F, P, z))
+                    z2 = zs[(t + 1) % len(zs)] if t else PL.rand_elt(rng)
+                    put("generic", a + self.enc(F, *self.xyzz(F, Q, z2)), G.add(P, Q))
+                    # the same point under two different Z: xyzz_dbl_slow
+                    put("P + P other Z", a + self.enc(F, *self.xyzz(F, P, PL.rand_elt(rng))), G.add(P, P))
+                    put("P + (-P) other Z", a + self.enc(F, *self.xyzz(F, G.neg(P), PL.rand_elt(rng))), None)
+                    I = ids[(i + t) % len(ids)]
+                    put("addend identity", a + self.enc(F, *I), P)
+                    put("acc identity", self.enc(F, *I) + a, P)
+                z = PL.rand_elt(rng)
+                a = self.enc(F, *self.xyzz(F, P, z))
+                put("P + P same Z", a + a, G.add(P, P))
+                put("P + (-P) same Z", a + self.enc(F, *self.xyzz(F, G.neg(P), z)), None)
+            for I in ids:
+                for J in ids:
+                    put("identity + identity", self.enc(F, *I) + self.enc(F, *J), None)
+        elif b in ("to_affine", "store_jacobian"):
+            for P in pts:
+                for z in self.zs(F, rng, 4):
+                    put("generic", self.enc(F, *self.xyzz(F, P, z)), P)
+            for I in ids:
+                put("identity", self.enc(F, *I), None)
+        else:
+            assert b == "from_jacobian"
+            for P in pts:
+                for z in self.zs(F, rng, 4):
+                    put("generic", self.enc(F, Fo.mul(P[0], Fo.sqr(z)), Fo.mul(P[1], Fo.mul(Fo.sqr(z), z)), z), P)
+            for X, Y in ((Fo.zero, Fo.one), (Fo.one, Fo.one), (Fo.zero, Fo.zero), (PL.rand_elt(rng), PL.rand_elt(rng))):
+                put("identity", self.enc(F, X, Y, Fo.zero), None)
+        return out
+
+    def pre(self, F, ctx):
+        assert ctx[1] is None or self.PL(F).G.on_curve(ctx[1])
+
+    def check_xyzz(self, F, row, want, tag):
+        Fo = self.PL(F).G.F
+        x, y, zz, zzz = self.dec(F, row, 4, tag)
+        if want is None:
+            assert Fo.is_zero(zz), f"{tag}: identity expected (zz == 0), got zz = {zz}"
+            return
+        assert not Fo.is_zero(zz), f"{tag}: the identity instead of {want}"
+        assert Fo.mul(Fo.sqr(zz), zz) == Fo.sqr(zzz), f"{tag}: zz^3 != zzz^2"
+        got = (Fo.mul(x, Fo.inv(zz)), Fo.mul(y, Fo.inv(zzz)))
+        assert got == want, f"{tag}: point is {got}, want {want}"
+
+    def check(self, F, ctx, row):
+        PL, Fo, W = self.PL(F), self.PL(F).G.F, self.W(F)
+        kind, want, extra = ctx
+        row = [int(v) for v in row]
+        tag = f"{self.kind} [{kind}]"
+        b = self.base
+        if b == "to_affine":
+            exp = self.enc(F, *want) if want is not None else [0] * (2 * W)           # the identity is the words (0, 0)
+            assert row[:2 * W] == exp, f"{tag}: got {self.dec(F, row, 2, tag)}, want {want}"
+        elif b == "store_jacobian":
+            X, Y, Z = self.dec(F, row, 3, tag)
+            if want is None:
+                assert (X, Y, Z) == (Fo.zero, Fo.one, Fo.zero), f"{tag}: the identity is (0, 1, 0), got {(X, Y, Z)}"
+                return
+            assert not Fo.is_zero(Z), f"{tag}: Z == 0 for {want}"
+            z2 = Fo.sqr(Z)
+            z6 = Fo.mul(Fo.sqr(z2), z2)
+            assert Fo.sqr(Y) == Fo.add(Fo.mul(Fo.sqr(X), X), Fo.mul(PL.G.b, z6)), f"{tag}: Y^2 != X^3 + b Z^6"
+            zi = Fo.inv(Z)
+            got = (Fo.mul(X, Fo.sqr(zi)), Fo.mul(Y, Fo.mul(Fo.sqr(zi), zi)))
+            assert got == want, f"{tag}: point is {got}, want {want}"
+        elif b == "madd_fast":
+            ret_want, acc = extra
+            assert row[4 * W] == int(ret_want), f"{tag}: returned {row[4 * W]}, want {int(ret_want)}"
+            if not ret_want:
+                assert row[:4 * W] == acc, f"{tag}: returned false but changed the accumulator"
+            else:
+                self.check_xyzz(F, row, want, tag)
+        else:
+            self.check_xyzz(F, row, want, tag)
+
+
 # ------------------------------------------------------------------------------------------------------------ registry
 OPS = {}
 for _k in ("fp_add", "fp_sub", "fp_neg", "fp_dbl", "fp_mul", "fp_sqr", "fp_reduce_once", "fp_to_mont", "fp_from_mont", "fp_inv", "fp_pow_u64"):
@@ -1115,10 +1313,13 @@ QUAD_OF = {"quad_add_mem": "bk_add_mem", "quad_dbl_mem": "bk_dbl_mem", "quad_add
 OPS["quad_add_mem"] = BkAddMemOp("quad_add_mem", 1)
 OPS["quad_dbl_mem"] = BkDblMemOp("quad_dbl_mem", 1)
 OPS["quad_add_mem2"] = BkAddMemOp("quad_add_mem2", 2, ["Bn254Fq"])
+for _k in EcOp.KINDS:                                       # saturated XYZZ<Fp<P>> / XYZZ<Fp2<P>> (ec_dev.hpp)
+    OPS["ec_" + _k] = EcOp("ec_" + _k, 1)
+    OPS["ec2_" + _k] = EcOp("ec2_" + _k, 2)
 
 LAYER_OF = {}
 for _k in OPS:
-    LAYER_OF[_k] = ("fp" if _k.startswith("fp") else "fu" if _k.startswith("fu_") else "accumulate" if _k.startswith("xyzz") else
+    LAYER_OF[_k] = ("fp" if _k.startswith("fp") else "ec" if _k.startswith("ec") else "fu" if _k.startswith("fu_") else "accumulate" if _k.startswith("xyzz") else
                     "quad" if _k.startswith("quad") else "bucket")
 
 

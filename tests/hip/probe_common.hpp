@@ -1,4 +1,4 @@
-// Test-only probe of the device arithmetic (field_dev.hpp, unsat_dev.hpp, bucket_dev.hpp, coop_dev.hpp): every primitive behind
+// Test-only probe of the device arithmetic (field_dev.hpp, unsat_dev.hpp, bucket_dev.hpp, coop_dev.hpp, ec_dev.hpp): every primitive behind
 // its own tiny kernel, one lane per case, raw uint32 limbs in and out.  The product headers are included unchanged; nothing here
 // is linked into libzkp_accel.so.  The reference is Python integer arithmetic (tests/field_ref.py).
 //

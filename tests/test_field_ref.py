@@ -165,3 +165,105 @@ def test_probe_cross_compiles():
     lib = field_probe.build()
     assert lib.exists()
     assert hasattr(ctypes.CDLL(str(lib)), "zkp_probe_run")
+
+
+def _ec_model(spec, F, words):
+    """The formulas of ec_dev.hpp (dbl-2008-s-1, madd-2008-s, add-2008-s, a = 0) over oracle/pyref field elements: the words a
+    correct device returns for the input row `words`."""
+    Fo, W, b = spec.PL(F).G.F, spec.W(F), spec.base
+    inf = [Fo.one, Fo.one, Fo.zero, Fo.zero]
+    sub, mul, sqr, dbl_ = Fo.sub, Fo.mul, Fo.sqr, lambda a: Fo.small(a, 2)
+
+    def dbl(p, aff=False):
+        x, y = p[0], p[1]
+        if (aff and Fo.is_zero(x) and Fo.is_zero(y)) or (not aff and Fo.is_zero(p[2])) or Fo.is_zero(y):
+            return inf
+        u = dbl_(y)
+        v = sqr(u)
+        w = mul(u, v)
+        s = mul(x, v)
+        m = Fo.small(sqr(x), 3)
+        x3 = sub(sqr(m), dbl_(s))
+        y3 = sub(mul(m, sub(s, x3)), mul(w, y))
+        return [x3, y3, v, w] if aff else [x3, y3, mul(v, p[2]), mul(w, p[3])]
+
+    def add(p, o, fast=False):
+        """o: XYZZ; an affine addend comes as (x, y, 1, 1) or, for the identity, with zz = 0."""
+        if Fo.is_zero(o[2]):
+            return p, True
+        if Fo.is_zero(p[2]):
+            return list(o), True
+        u1, u2, s1, s2 = mul(p[0], o[2]), mul(o[0], p[2]), mul(p[1], o[3]), mul(o[1], p[3])
+        pp_, r = sub(u2, u1), sub(s2, s1)
+        if Fo.is_zero(pp_):
+            if fast:
+                return p, False
+            return (dbl(p) if Fo.is_zero(r) else inf), True
+        pp = sqr(pp_)
+        ppp = mul(pp_, pp)
+        q = mul(u1, pp)
+        x3 = sub(sub(sqr(r), ppp), dbl_(q))
+        y3 = sub(mul(r, sub(q, x3)), mul(s1, ppp))
+        return [x3, y3, mul(mul(p[2], o[2]), pp), mul(mul(p[3], o[3]), ppp)], True
+    n_in = {"dbl_affine": 2, "dbl": 4, "madd": 6, "madd_fast": 6, "add": 8, "to_affine": 4, "store_jacobian": 4, "from_jacobian": 3}[b]
+    c = spec.dec(F, words, n_in, "model input")
+    if b == "dbl_affine":
+        return spec.enc(F, *dbl(c, aff=True))
+    if b == "dbl":
+        return spec.enc(F, *dbl(c))
+    if b in ("madd", "madd_fast"):
+        o = [c[4], c[5]] + ([Fo.zero, Fo.zero] if Fo.is_zero(c[4]) and Fo.is_zero(c[5]) else [Fo.one, Fo.one])
+        res, ret = add(c[:4], o, fast=b == "madd_fast")
+        return spec.enc(F, *res) + ([int(ret)] if b == "madd_fast" else [])
+    if b == "add":
+        return spec.enc(F, *add(c[:4], c[4:])[0])
+    if b == "to_affine":
+        if Fo.is_zero(c[2]):
+            return spec.enc(F, Fo.zero, Fo.zero)
+        return spec.enc(F, mul(c[0], Fo.inv(c[2])), mul(c[1], Fo.inv(c[3])))
+    if b == "store_jacobian":
+        if Fo.is_zero(c[2]):
+            return spec.enc(F, Fo.zero, Fo.one, Fo.zero)
+        t = mul(c[2], sqr(c[3]))
+        return spec.enc(F, mul(c[0], t), mul(mul(c[1], t), sqr(c[2])), mul(c[2], c[3]))
+    if Fo.is_zero(c[2]):
+        return spec.enc(F, *inf)
+    return spec.enc(F, c[0], c[1], sqr(c[2]), mul(sqr(c[2]), c[2]))
+
+
+@pytest.mark.parametrize("op,field", [(op, f) for op in sorted(R.OPS) if R.LAYER_OF[op] == "ec" for f in R.OPS[op].fields])
+def test_ec_checker_against_formula_model(op, field):
+    """The checks of the ec_dev.hpp operations accept what the header's formulas give in Python integers on every generated case
+    (so the expected points, built from the affine group law alone, are right) and reject a row with one word changed, the
+    negated point, and a non-canonical coordinate."""
+    spec, F = R.OPS[op], R.FIELDS[field]
+    cases = R.make_cases(op, field)
+    kinds = {c[2][0] for c in cases}
+    assert {"generic", "identity"} <= kinds or {"generic", "P + P", "P + (-P)", "acc identity", "addend identity", "identity + identity"} <= kinds \
+        or {"generic", "P + P other Z", "P + P same Z", "P + (-P) other Z", "acc identity", "addend identity", "identity + identity"} <= kinds
+    rng = random.Random(9)
+    W = spec.W(F)
+    for n, (words, init, ctx) in enumerate(cases):
+        assert len(words) == len(cases[0][0])
+        row = _ec_model(spec, F, words)
+        assert len(row) == spec.nout(F)
+        spec.check(F, ctx, row)
+        if ctx[1] is None or (spec.base == "madd_fast" and not ctx[2][0]):
+            continue
+        if n % 8 == 0:
+            bad = list(row)
+            bad[rng.randrange(len(row) - (spec.base == "madd_fast"))] ^= 1 << rng.randrange(8)
+            with pytest.raises(AssertionError):
+                spec.check(F, ctx, bad)
+            bad = list(row)                                 # -P: y -> p - y in the first component
+            y = F.from_words(row[W:W + F.N])
+            if y:
+                bad[W:W + F.N] = F.words(F.p - y)
+                with pytest.raises(AssertionError):
+                    spec.check(F, ctx, bad)
+            bad = list(row)                                 # x + p: right mod p, not canonical
+            x = F.from_words(row[:F.N]) + F.p
+            if x < F.R:
+                bad[:F.N] = F.words(x)
+                with pytest.raises(AssertionError):
+                    spec.check(F, ctx, bad)

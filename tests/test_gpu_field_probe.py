@@ -1,10 +1,12 @@
-"""Device field and bucket-point arithmetic, primitive by primitive, against Python integers (tests/field_ref.py), with the
-operands at the top of the ranges their call sites declare.  Each test runs one operation of the probe library (tests/hip/,
+"""Device field, bucket-point and saturated curve-point arithmetic, primitive by primitive, against Python integers
+(tests/field_ref.py), with the operands at the top of the ranges their call sites declare and, for the XYZZ points of ec_dev.hpp,
+at every exceptional case of the group law.  Each test runs one operation of the probe library (tests/hip/,
 built by tests/field_probe.py) over all generated cases, one lane per case, and checks every row; nothing is filtered on the
 device's answer.  A failure names the primitive: "fu-fu_sub_sel<2>-Bls381Fq", not "the 2^22 MSM differs".
 
 Measured on an MI355X: the whole file (about 390 000 cases) takes 6 s; a device call is 0.1 to 1.2 ms, case generation and the
-Python reference are the rest.
+Python reference are the rest.  The 32 tests of the ec_dev.hpp operations ("ec-..."; 20 844 cases) add 2 s: a device call is
+0.1 ms, the slowest test (ec2_add on Bls381Fq, 1584 cases) 0.12 s.
 """
 import os
 import time

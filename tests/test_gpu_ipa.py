@@ -10,6 +10,7 @@ from ckb_zkp_amd import codec, ipa
 from ckb_zkp_amd.params import get_curve
 from oracle import cpu_oracle
 from oracle.pyref.curves import Group
+from tests import glv_ref
 from tests.util import OC, random_points, to_abi_points
 
 pytestmark = pytest.mark.gpu
@@ -68,13 +69,19 @@ def test_against_pyref(ctx, curve):
     Q[7] = G.neg(P[7])                                            # L = -R, a = b: the identity
     P[8] = None                                                   # flagged identity
     cases = [(0, 5), (7, 0), (1, r - 1), (12345, 12345), (r - 1, 1), (2, 3), (9, 9), (4, 4), (3, 5), (0, 0), (r - 2, r - 3), (1, 1)]
+    # the scalars at the edges of the GLV split of a and b (tests/test_glv_split.py): lambda, lambda + 1, r - lambda and the picks
+    # of the CPU run (largest parts, zero parts, each reachable sign pair); these are checked in every column
+    gl = glv_ref.Glv(curve)
+    edge = [gl.lam, gl.lam + 1, r - gl.lam] + [e for _, e in glv_ref.GLV_EDGE[curve]]
+    cases += [(e, edge[(i + 1) % len(edge)]) for i, e in enumerate(edge)] + [(e, e) for e in edge[:3]] + [(1, gl.lam), (gl.lam, 1)]
     L, Li = to_abi_points(curve, 1, P)
     R, Ri = to_abi_points(curve, 1, Q)
     for k, (a, b) in enumerate(cases):
         xy, inf = ctx.ipa_fold(c, L, Li, R, Ri, _mont(c, a), _mont(c, b))
         got = codec.g1_from_mont(xy, inf, c)
-        exp = G.add(G.mul(P[k], a) if P[k] else None, G.mul(Q[k], b))
-        assert got[k] == exp, (k, a, b)
+        for j in ([k] if k < 12 else range(12)):
+            exp = G.add(G.mul(P[j], a) if P[j] else None, G.mul(Q[j], b))
+            assert got[j] == exp, (k, j, a, b)
     xy, inf = ctx.ipa_fold(c, L, Li, R, Ri, _mont(c, 4), _mont(c, 4))
     assert inf[7] == 1 and not xy[7].any()
 
