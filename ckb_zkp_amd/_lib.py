@@ -173,6 +173,8 @@ SIGNATURES = {
     "zkp_fr_bp_t_coeffs_dev": (C.c_int32, [vp, C.c_int, C.POINTER(BpVectors), vp, vp, vp]),
     "zkp_fr_bp_lr_eval_dev": (C.c_int32, [vp, C.c_int, C.POINTER(BpVectors), vp, vp, vp, vp, vp, vp]),
     "zkp_fr_ipa_fold_ab_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp, vp]),
+    "zkp_fr_asvc_subset_weights_dev": (C.c_int32, [vp, C.c_int, C.c_uint32, vp, C.c_size_t, vp, vp]),
+    "zkp_fr_asvc_quotient_dev": (C.c_int32, [vp, C.c_int, vp, C.c_uint32, vp, C.c_size_t, vp]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

@@ -398,6 +398,23 @@ class Context:
                                                    _ptr(_c64(x)), _ptr(out)), "zkp_fr_ipa_fold_ab_dev")
         return out
 
+    def fr_asvc_subset_weights_dev(self, curve, log_n: int, positions, out_ptr: int = 0, want_host: bool = True):
+        """zkp_fr_asvc_subset_weights_dev: c_i = 1 / prod_{j != i} (w^p_i - w^p_j) for the distinct positions p_i < 2^log_n, into the
+        DEVICE buffer out_ptr (k Fr, 0: none) and / or returned as (k, 4) uint64 Montgomery (None without want_host)."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32)
+        out = np.zeros((len(pos), 4), dtype=np.uint64) if want_host else None
+        _lib.check(self.lib.zkp_fr_asvc_subset_weights_dev(self.h, get_curve(curve).cid, log_n, _ptr(pos), len(pos),
+                                                           C.c_void_p(out_ptr or 0), _ptr(out)), "zkp_fr_asvc_subset_weights_dev")
+        return out
+
+    def fr_asvc_quotient_dev(self, curve, phi_ptr: int, log_n: int, positions, q_ptr: int):
+        """zkp_fr_asvc_quotient_dev: q = floor(Phi / prod_i (X - w^p_i)) over DEVICE Montgomery Fr: 2^log_n coefficients in,
+        2^log_n - k out.  Launches only."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32)
+        _lib.check(self.lib.zkp_fr_asvc_quotient_dev(self.h, get_curve(curve).cid, C.c_void_p(phi_ptr or 0), log_n, _ptr(pos), len(pos),
+                                                     C.c_void_p(q_ptr or 0)), "zkp_fr_asvc_quotient_dev")
+        self.sync()                                               # `pos` is host memory of this call
+
     def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
         """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
         Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""

@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "asvc.hpp"
 #include "bulletproofs.hpp"
 #include "ctx.hpp"
 #include "gkr.hpp"
@@ -877,6 +878,16 @@ int32_t zkp_marlin_prove(zkp_ctx* ctx, zkp_marlin_index* index, uint64_t powers_
   return guarded(ctx, [&] {
     marlin_prove(ctx, index, powers_of_g, powers_of_gamma_g, ivk_bytes, ivk_len, x, w, n_w, rnd, fixed_challenges, out);
   });
+}
+int32_t zkp_fr_asvc_subset_weights_dev(zkp_ctx* ctx, zkp_curve_t curve, uint32_t log_n, const uint32_t* positions_host, size_t k,
+                                       uint64_t* weights_dev, uint64_t* weights_host) {
+  if (!positions_host || (!weights_dev && !weights_host)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { asvc_subset_weights(ctx, curve, log_n, positions_host, k, weights_dev, weights_host); });
+}
+int32_t zkp_fr_asvc_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* phi_dev, uint32_t log_n,
+                                 const uint32_t* positions_host, size_t k, uint64_t* q_dev) {
+  if (!phi_dev || !positions_host || !q_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { asvc_quotient(ctx, curve, phi_dev, log_n, positions_host, k, q_dev); });
 }
 int32_t zkp_bench_mulmod(zkp_ctx* ctx, zkp_curve_t curve, int32_t field, int32_t unsaturated, double* out) {
   if (!out || (curve != ZKP_BN254 && curve != ZKP_BLS12_381) || field < 0 || field > 1) return ZKP_ERR_BAD_ARG;

@@ -55,7 +55,8 @@ const char* zkp_status_string(int32_t status);
  * then zkp_fr_prefix_product_dev / zkp_fr_plonk_perm_z_dev / zkp_fr_plonk_quotient_dev (PLONK rounds 2 and 3),
  * then zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev (PLONK evaluations and opening polynomials),
  * then zkp_fr_gkr_eval_layer_batch_dev / zkp_fr_gkr_dp_round_dev (Hyrax data-parallel GKR),
- * then zkp_fr_powers_dev / zkp_fr_bp_t_coeffs_dev / zkp_fr_bp_lr_eval_dev / zkp_fr_ipa_fold_ab_dev (Bulletproofs R1CS prover).
+ * then zkp_fr_powers_dev / zkp_fr_bp_t_coeffs_dev / zkp_fr_bp_lr_eval_dev / zkp_fr_ipa_fold_ab_dev (Bulletproofs R1CS prover),
+ * then zkp_fr_asvc_subset_weights_dev / zkp_fr_asvc_quotient_dev (aSVC subvector commitments).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -440,6 +441,37 @@ int32_t zkp_fr_bp_lr_eval_dev(zkp_ctx* ctx, zkp_curve_t curve, const zkp_bp_vect
  * ZKP_ERR_BAD_ARG: a NULL or misaligned a_dev / b_dev, n outside the rule, a and b overlapping, *x_host == 0 or >= r. */
 int32_t zkp_fr_ipa_fold_ab_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* a_dev, uint64_t* b_dev, size_t n, const uint64_t* x_host,
                                uint64_t* c_out_host);
+/* aSVC subvector commitments (later in 0.7.1, detected by symbol): the Fr work of asvc/src/lib.rs that no earlier entry covers.
+ * `commit` is zkp_msm_g1_mont_dev over a resident Lagrange-basis key, prove_pos (:182-225) an inverse zkp_ntt_dev, the quotient
+ * below and zkp_msm_g1_mont_dev over the powers of tau; the updates and aggregate_proofs are small variable-base MSMs.
+ * The domain is the one of zkp_ntt_dev: n = 2^log_n, w its root of unity, 1 <= log_n <= min(30, two-adicity) (above:
+ * ZKP_ERR_DOMAIN_TOO_LARGE).  positions_host: k distinct positions p_i < n, host memory, any order, 1 <= k <=
+ * min(n, ZKP_ASVC_MAX_POSITIONS).  Vectors: Fr, Montgomery, canonical, 16-byte aligned, device memory.  Every element written is
+ * the canonical Montgomery representative (bit-exact results).  Every argument is checked before anything runs: on an error every
+ * output is untouched.
+ *
+ * The weights c_i = 1 / A_I'(w^p_i) = 1 / prod_{j != i} (w^p_i - w^p_j) of A_I(X) = prod_i (X - w^p_i), the coefficients of
+ * aggregate_proofs (:425-431), in the order of positions_host: the k^2 differences are multiplied on the device (one workgroup per
+ * position), then ONE batch inversion.  k == 1 gives 1.  At least one of weights_dev (k Fr) and weights_host (k Fr) is given; with
+ * weights_host the call returns after the copy, otherwise it only launches.  Three launches.
+ * ZKP_ERR_BAD_ARG: log_n == 0, k outside the rule, a position >= n, a repeated position, both outputs NULL, a misaligned weights_dev. */
+#define ZKP_ASVC_MAX_POSITIONS 1024
+int32_t zkp_fr_asvc_subset_weights_dev(zkp_ctx* ctx, zkp_curve_t curve, uint32_t log_n, const uint32_t* positions_host, size_t k,
+                                       uint64_t* weights_dev, uint64_t* weights_host);
+/* q = floor(Phi / A_I) (the divide_with_q_and_r of :197-212): phi_dev holds the n coefficients of Phi, q_dev receives the n - k
+ * coefficients of the quotient; k == n writes nothing.  With w_i = w^p_i and the weights c_i above,
+ *   q[t] = sum_i c_i S_i[t],   S_i[t] = Phi[t+1] + w_i S_i[t+1],  S_i[n-1] = 0:
+ * k first-order suffix recurrences combined with k weights; the arithmetic is exact, so q equals long division bit for bit.
+ * The recurrences are cut into segments of L = 2^floor(log2 k) coefficients.  Because sum_i c_i w_i^m = 0 for m < k - 1 and L <= k,
+ * what a segment's own coefficients contribute cancels, and q[t] = sum_i c_i E_i[s] w_i^d with E_i[s] the value of S_i at the top of
+ * t's segment s and d the distance of t below that top.  One pass forms the segment heads sum_j Phi[sL + j] w_i^j (four positions
+ * share each coefficient load), a blocked suffix scan with the ratios w_i^L turns them into c_i E_i[s] in place (n k / L <= 2 n
+ * elements of scratch, nothing of size n k), and one pass accumulates eight consecutive q[t] per thread over all positions in
+ * registers and writes each once.  About 2 + 3 / L products per (coefficient, position).  Nine launches whatever k is; Phi is read
+ * once per four positions (the re-reads hit the cache: all positions of a segment run side by side).  Launches only, like
+ * zkp_fr_vec_op_dev.  ZKP_ERR_BAD_ARG: the rules above, a NULL or misaligned phi_dev / q_dev, q_dev overlapping phi_dev. */
+int32_t zkp_fr_asvc_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* phi_dev, uint32_t log_n,
+                                 const uint32_t* positions_host, size_t k, uint64_t* q_dev);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
