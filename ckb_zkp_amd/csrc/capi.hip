@@ -420,7 +420,14 @@ static int32_t msm_common(zkp_ctx* ctx, int group, uint64_t handle, size_t offse
       ZKP_HIP(hipMemcpyAsync(d, scalars, n * 32, hipMemcpyHostToDevice, ctx->cur->stream));
       sdev = d;
     }
-    msm_run(ctx, handle, offset, sdev, n, montgomery, out);
+    MsmJob job;
+    job.handle = handle;
+    job.offset = offset;
+    job.scalars_dev = sdev;
+    job.n = n;
+    job.montgomery = montgomery;
+    job.out_xyz_host = out;
+    msm_run(ctx, job);
   });
 }
 int32_t zkp_msm_g1(zkp_ctx* ctx, uint64_t h, size_t off, const uint64_t* s, size_t n, uint64_t* out) {

@@ -52,7 +52,7 @@ struct zkp_groth16_pk {
   DevCsr m[3];
   uint64_t hA = 0, hB1 = 0, hB2 = 0, hH = 0, hL = 0;
   bool share_b_sort = false;     // b_g1_query / b_g2_query: same length, window configuration and identity pattern
-  bool chain_lh = false;         // H accumulates into L's buckets: one bucket reduction for l' + h_acc (bucket chaining, ctx.hpp)
+  bool chain_lh = false;         // H accumulates into L's buckets: one bucket reduction for l' + h_acc (bucket chaining, internal.hpp MsmJob)
   bool share_al_sort = false;    // L (stored index-aligned with z) reuses A's bucket sort: same scalars, same identity pattern
   bool share_l1 = false;         // A, L and (b_in_l1) B2 (+B1) share ONE level-1 sort pass over z (each filters its identities at level 2)
   bool b_in_l1 = false;          // the B queries have A's window configuration and take part in the shared pass
@@ -851,7 +851,9 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
       ZKP_REQUIRE(hg == h + (size_t)g * h_stride * 8, ZKP_ERR_BAD_ARG);     // h sits at the same place in every region
     }
   };
-  auto run = [&](int idx, uint64_t handle, const uint64_t* sc, size_t n, int w, int sort_src = -1, int l1_src = -1) {
+  // defer_reduce / acc_into: the L -> H bucket chain (MsmJob)
+  auto run = [&](int idx, uint64_t handle, const uint64_t* sc, size_t n, int w, int sort_src = -1, int l1_src = -1,
+                 bool defer_reduce = false, int acc_into = -1) {
     float ms = 0.f, ms_sc = 0.f;
     uint64_t e = 0;
     static const char* const names[5] = {"A", "B1", "B2", "H", "L"};
@@ -860,8 +862,24 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
 #ifdef ZKP_ABLATION   // timing ablation builds only (ZKP_BUILD_DEFS=-DZKP_ABLATION -> variants/<tag>/): WRONG proofs, never in the shipped library
     ctx->dbg_skip_k8 = ((tune.debug_skip_k8_mask >> idx) & 1) && ctx->batch_mode;
 #endif
-    msm_run(ctx, handle, 0, sc, n, true, nullptr, res + idx * slot, prof ? &ms : nullptr, &e, fan ? w : 0,
-            fan ? sort_src : -1, prof ? &ms_sc : nullptr, fan ? l1_src : -1, G, idx == 3 ? h_stride : s_stride, 6 * slot);
+    MsmJob job;
+    job.handle = handle;
+    job.scalars_dev = sc;
+    job.n = n;
+    job.montgomery = true;
+    job.out_dev_xyzz = res + idx * slot;
+    job.ms_accumulate = prof ? &ms : nullptr;
+    job.ms_scan = prof ? &ms_sc : nullptr;
+    job.n_entries = &e;
+    job.ws = fan ? w : 0;
+    job.sort_src = fan ? sort_src : -1;
+    job.l1_src = fan ? l1_src : -1;
+    job.sets = G;
+    job.set_stride = idx == 3 ? h_stride : s_stride;
+    job.out_stride = 6 * slot;
+    job.defer_reduce = defer_reduce;
+    job.acc_into = acc_into;
+    msm_run(ctx, job);
     ctx->dbg_skip_k8 = false;
     toc(&tm.ms_msm[idx]);
     acc_ms += ms;
@@ -915,8 +933,8 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
         g2_done_in_fan = true;
       }
       run(1, pk->hB1, Sd + 4 * pk->q_lo[1], pk->q_n[1], 3, pk->share_b_sort ? 2 : -1);
-      ctx->msm_defer_reduce = chained = pk->chain_lh;
-      run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 1, pk->share_al_sort ? 1 : -1, l1);   // A's sort / level-1 pass, still in this workspace
+      chained = pk->chain_lh;                          // L's buckets stay in workspace 1 for H to reduce with its own
+      run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 1, pk->share_al_sort ? 1 : -1, l1, chained);   // A's sort / level-1 pass, still in this workspace
       if (!partial_out) {
         ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[3].stream, ctx->cur->ev_a, 0));
         v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, G);
@@ -950,8 +968,8 @@ static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t*
     run(1, pk->hB1, Sd + 4 * pk->q_lo[1], pk->q_n[1], 0);
     run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 0);
   }
-  if (chained) ctx->msm_acc_into = 1;                 // on top of L's buckets (workspace 1): result slot 3 = h_acc + l', slot 4 = identity
-  run(3, pk->hH, reinterpret_cast<const uint64_t*>(h) + 4 * pk->q_lo[3], pk->q_n[3], 0);  // :186-187 (min(len) truncation in q_n)
+  // chained: on top of L's buckets (workspace 1): result slot 3 = h_acc + l', slot 4 = identity
+  run(3, pk->hH, reinterpret_cast<const uint64_t*>(h) + 4 * pk->q_lo[3], pk->q_n[3], 0, -1, -1, false, chained ? 1 : -1);  // :186-187 (min(len) truncation in q_n)
   if (!(fan && l_done_in_fan)) run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 0);                                 // :189-190
   if (fan) {
     for (int w = 1; w < zkp_ctx::N_WS; w++) {
@@ -1619,8 +1637,16 @@ void prove_multi_t(zkp_ctx* root, zkp_groth16_pk_multi* M, const uint64_t* const
     }
     const uint64_t* Sd = reinterpret_cast<const uint64_t*>(S[k]);
     auto run = [&](int idx, uint64_t handle, int w, int sort_src, int l1_src) {
-      msm_run(ctx, handle, 0, Sd + 4 * pk->q_lo[idx], pk->q_n[idx], true, nullptr, res[k] + idx * slot, nullptr, nullptr, w,
-              sort_src, nullptr, l1_src);
+      MsmJob job;
+      job.handle = handle;
+      job.scalars_dev = Sd + 4 * pk->q_lo[idx];
+      job.n = pk->q_n[idx];
+      job.montgomery = true;
+      job.out_dev_xyzz = res[k] + idx * slot;
+      job.ws = w;
+      job.sort_src = sort_src;
+      job.l1_src = l1_src;
+      msm_run(ctx, job);
     };
     const int l1 = pk->share_l1 ? 1 : -1;
     const bool b_l1 = pk->share_l1 && pk->b_in_l1;
@@ -1664,8 +1690,13 @@ void prove_multi_t(zkp_ctx* root, zkp_groth16_pk_multi* M, const uint64_t* const
     zkp_groth16_pk* pk = M->pk[k];
     ZKP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->cur->stream;
-    msm_run(ctx, pk->hH, 0, reinterpret_cast<const uint64_t*>(h[k]) + 4 * pk->q_lo[3], pk->q_n[3], true, nullptr,
-            res[k] + 3 * slot, nullptr, nullptr, 0);
+    MsmJob job;
+    job.handle = pk->hH;
+    job.scalars_dev = reinterpret_cast<const uint64_t*>(h[k]) + 4 * pk->q_lo[3];
+    job.n = pk->q_n[3];
+    job.montgomery = true;
+    job.out_dev_xyzz = res[k] + 3 * slot;
+    msm_run(ctx, job);
     for (int w = 1; w < zkp_ctx::N_WS; w++) {
       ZKP_HIP(hipEventRecord(ctx->cur->ws[w].done, ctx->cur->ws[w].stream));
       ZKP_HIP(hipStreamWaitEvent(st, ctx->cur->ws[w].done, 0));

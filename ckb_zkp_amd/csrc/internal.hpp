@@ -51,16 +51,38 @@ void bases_free(zkp_ctx* ctx, uint64_t handle);
 uint64_t bases_share(zkp_ctx* dst, zkp_ctx* src, uint64_t handle);
 size_t bases_len(zkp_ctx* ctx, uint64_t handle);
 int bases_group(zkp_ctx* ctx, uint64_t handle);
-// result -> host Jacobian (out_xyz_host) ; if out_dev_xyzz != nullptr the XYZZ result is also left on device
-// runs on workspace `ws` (its stream + scratch); does not synchronise unless out_xyz_host != nullptr
-void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scalars_dev, size_t n, bool montgomery,
-             uint64_t* out_xyz_host, void* out_dev_xyzz = nullptr, float* ms_accumulate = nullptr,
-             uint64_t* n_entries = nullptr, int ws = 0, int sort_src = -1, float* ms_scan = nullptr, int l1_src = -1,
-             int sets = 1, size_t set_stride = 0, size_t out_stride = 0);
-// sets == 2: ONE kernel chain computes `sets` MSMs over the same resident bases — scalar vector g lies set_stride scalars
-// behind vector g - 1 and its XYZZ result out_stride bytes behind result g - 1 (out_dev_xyzz only, no host read-back).  Sort
-// sharing (sort_src, l1_src) and bucket chaining work as for one MSM when both partners use the same `sets`.  msm_sets_ok: whether
-// this base vector and the context's switches allow it (fixed-base plan, fused pyramid top).
+// One MSM over the resident base vector `handle`: sum_i scalars[i] * bases[offset + i], i < n.  Everything the call needs is in
+// this request; nothing is remembered from one MSM to the next.
+struct MsmJob {
+  uint64_t handle = 0;
+  size_t offset = 0;
+  const uint64_t* scalars_dev = nullptr;
+  size_t n = 0;
+  bool montgomery = false;
+  uint64_t* out_xyz_host = nullptr;    // != nullptr: the Jacobian result is read back, and only then does the call synchronise
+  void* out_dev_xyzz = nullptr;        // != nullptr: the XYZZ result is also left on the device
+  int ws = 0;                          // the workspace (its stream + scratch) of the current lane the MSM runs on
+  int sort_src = -1, l1_src = -1;      // sort sharing, see below
+  // sets == 2: ONE kernel chain computes `sets` MSMs over the same resident bases — scalar vector g lies set_stride scalars
+  // behind vector g - 1 and its XYZZ result out_stride bytes behind result g - 1 (out_dev_xyzz only, no host read-back).  Sort
+  // sharing and bucket chaining work as for one MSM when both partners use the same `sets`.
+  int sets = 1;
+  size_t set_stride = 0, out_stride = 0;
+  // profiling outputs: milliseconds of the accumulate kernels / of the scalar scan (measured only while the context profiles,
+  // else 0); entries sorted (nominal n * windows * sets; the exact count while profiling)
+  float* ms_accumulate = nullptr;
+  float* ms_scan = nullptr;
+  uint64_t* n_entries = nullptr;
+  // Bucket chaining: two MSMs whose results are only ever ADDED (Groth16: L and H, C = ... + l' + h_acc; the chunks of a chunked
+  // MSM) share ONE bucket array and ONE reduction.  defer_reduce: this MSM stops after its buckets are complete (result = the
+  // identity).  acc_into >= 0: it accumulates on top of the deferred buckets that workspace holds and reduces the sum.
+  // bucket_ws >= 0: it keeps its buckets in the bucket array of that workspace.  G1 fixed-base plans with n > 0 only.
+  bool defer_reduce = false;
+  int acc_into = -1;
+  int bucket_ws = -1;
+};
+void msm_run(zkp_ctx* ctx, const MsmJob& job);
+// msm_sets_ok: whether this base vector and the context's switches allow MsmJob::sets (fixed-base plan, fused pyramid top).
 bool msm_sets_ok(zkp_ctx* ctx, uint64_t handle, int sets);
 // bench_kern.hip: sustained rate (1e9 products/s) of the library's Montgomery multipliers; field 0 = Fr, 1 = Fq
 double bench_mulmod(zkp_ctx* ctx, int curve, int field, bool unsaturated);
@@ -72,7 +94,7 @@ bool bases_same_shape(zkp_ctx* ctx, uint64_t h1, uint64_t h2);
 // flags (n bytes, host) the digit scan of `handle` uses instead of the entry's own identity flags when it sorts for a group
 // of MSMs over the same scalars (a point is dropped only if it is the identity in every member)
 void bases_set_sort_flags(zkp_ctx* ctx, uint64_t handle, const uint8_t* flags_host, size_t n);
-// l1_src (msm_run): workspace of the same lane whose LEVEL-1 sort output (entries of a group of queries over the same scalars,
+// l1_src (MsmJob): workspace of the same lane whose LEVEL-1 sort output (entries of a group of queries over the same scalars,
 // scattered into bins) this MSM shares; it then runs its own level 2 and drops its own identities there.
 // bases_set_group: on the query that runs the shared pass; member_flags_host[i] bit k = base i is the identity in member k
 // (k < 3) although the group's scan (bases_set_sort_flags) keeps it.  bases_set_filter_bit: a member's k (-1 = none).

@@ -388,7 +388,13 @@ void marlin_index_commit(zkp_ctx* ctx, zkp_marlin_index* ix, uint64_t powers_g, 
   for (int m = 0; m < 3; m++)
     for (int q = 0; q < 4; q++) {
       std::vector<uint64_t> jac(jw64);
-      msm_run(ctx, powers_g, 0, ix->polys[m][q].p, ix->polys[m][q].n, true, jac.data());
+      MsmJob job;
+      job.handle = powers_g;
+      job.scalars_dev = ix->polys[m][q].p;
+      job.n = ix->polys[m][q].n;
+      job.montgomery = true;
+      job.out_xyz_host = jac.data();
+      msm_run(ctx, job);
       point_into_affine(ctx, ix->curve, 1, jac.data(), comms_xy + (size_t)(4 * m + q) * 12, inf + 4 * m + q);
     }
 }
@@ -493,8 +499,14 @@ struct EarlyMsms {
     ZKP_HIP(hipEventRecord(L->ev_fork, L->stream));                  // v is complete on the prover's stream
     ZKP_HIP(hipStreamWaitEvent(ws_st, L->ev_fork, 0));
     ZKP_REQUIRE(offset <= bases_len(ctx, handle), ZKP_ERR_BAD_ARG);
-    const size_t n = std::min(v.n, bases_len(ctx, handle) - offset);     // ark min(len) truncation, as msm_run_multi
-    msm_run(ctx, handle, offset, v.p, n, true, nullptr, nullptr, nullptr, nullptr, w);
+    MsmJob job;
+    job.handle = handle;
+    job.offset = offset;
+    job.scalars_dev = v.p;
+    job.n = std::min(v.n, bases_len(ctx, handle) - offset);             // ark min(len) truncation, as msm_run_multi
+    job.montgomery = true;
+    job.ws = w;
+    msm_run(ctx, job);
     ZKP_HIP(hipMemcpyAsync(ix->early_pinned + list.size() * SLOT, L->ws[w].out.p, jw64 * 8, hipMemcpyDeviceToHost, ws_st));
     ZKP_HIP(hipEventRecord(L->ws[w].done, ws_st));
     list.push_back({label, w, shifted, kind});

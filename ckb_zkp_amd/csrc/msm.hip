@@ -38,6 +38,7 @@
 #include "msm_digits.hpp"
 #include "msm_pyramid.hpp"
 #include "msm_small.hpp"
+#include "msm_sort_plan.hpp"
 #include "msm_vtbl.hpp"
 
 namespace zkp {
@@ -391,11 +392,7 @@ static void exclusive_scan_u32(hipStream_t st, const uint32_t* in, uint32_t* out
 //   level 2  one workgroup per bin (~16 K entries, <= 1024 distinct low keys): LDS histogram, LDS scan — which
 //            directly yields start/end of every bucket of the bin — and an LDS-atomic scatter of the values.
 // LDS atomics resolve same-bucket conflicts inside a wave in hardware; no global atomics on the data path.
-constexpr int SORT_H1_MAX = 13;        // level-1 bins <= 8192 (static LDS histogram, 32 KiB)
-constexpr uint32_t SORT_BIN_TARGET = 16384;   // entries per level-1 bin the level-2 kernel stages in LDS
-constexpr int SORT_L_MAX = 13;         // level-2 keys per bin <= 8192 (dynamic LDS)
-constexpr int SORT_SCALARS = 2048;    // default; larger MSMs use larger tiles (runtime `tile`) to keep the tile count ~1200
-constexpr int SORT_SCALARS_UNUSED_ = 0;     // scalars per workgroup in the level-1 passes (8 per lane): larger tiles = smaller (bin x tile) count matrix and longer contiguous runs per bin in the scatter (512 -> 2048: +2 % proofs/s)
+// The SORT_* constants and the geometry of a sort (bins, tiles, LDS sizes): msm_sort_plan.hpp.
 // NT = threads per workgroup.  Round 6: all workgroups of the level-1 passes are resident at once, so a pass lasts as long as ONE
 // workgroup; a tile's scalars are spread over more lanes (profiles/r06_sort_stage_ab.txt).
 template <class FrP, int NT>
@@ -524,10 +521,6 @@ __device__ __forceinline__ uint32_t wave_agg_inc(uint32_t* cnt, uint32_t idx, bo
 // write consecutive entries of one (bin, tile) run.  The one-entry-per-lane version above turns every 8-byte store into a
 // 32-byte fabric write (PMC: 9.0 M 32-byte + 2.3 M 64-byte write requests = 434 MB for 125 MB of entries); here a run of k
 // entries costs ceil(8k / 32) + 1 requests at most.  The bin id rides in bits 45..57 of the staged word (level 2 ignores them).
-#ifndef ZKP_SORT_STAGE_BYTES              // A/B builds (ZKP_BUILD_DEFS_msm): 28 KiB = five workgroups per CU instead of two
-#define ZKP_SORT_STAGE_BYTES (56 * 1024)
-#endif
-constexpr uint32_t SORT_STAGE_BYTES = ZKP_SORT_STAGE_BYTES;
 template <class FrP, int NT>
 __global__ __launch_bounds__(NT) void sort_scatter_staged_kernel(const uint32_t* __restrict__ scalars, size_t n,
                                                                   size_t offset, const uint8_t* __restrict__ inf,
@@ -623,11 +616,6 @@ __global__ __launch_bounds__(NT) void sort_scatter_staged_kernel(const uint32_t*
 //  by the LDS atomics on ~1000 random bins and the digit extraction, not by the store amplification), and level 2 got slower
 //  reading 1200 short runs per bin: A-query MSM 2.66 vs 2.37 ms, 106-108 vs 113 proofs/s.  Reverted; commit 'Level-1 bucket
 //  sort as ONE kernel per tile' holds the code.)
-constexpr uint32_t SORT_BIN_THREADS = 1024;
-#ifndef ZKP_SORT_BIN_STAGE                      // A/B builds: 18432 (72 KiB) lets two workgroups share a CU
-#define ZKP_SORT_BIN_STAGE 20480
-#endif
-constexpr uint32_t SORT_BIN_STAGE = ZKP_SORT_BIN_STAGE;      // values staged in LDS (80 KiB) so the output is written fully coalesced
 __global__ __launch_bounds__(SORT_BIN_THREADS) void sort_bin_kernel(const uint64_t* __restrict__ kv,
                                                                     const uint32_t* __restrict__ offs,
                                                                     uint32_t nblocks, int L,
@@ -695,7 +683,7 @@ __global__ __launch_bounds__(SORT_BIN_THREADS) void sort_bin_kernel(const uint64
 // bucket sizes this turns ~65 % lane utilisation into > 95 %, and it bounds the serial chain of any lane by CAP
 // even for adversarial inputs (all scalars equal) or the thinly populated top window.
 // tmeta layout (uint32): [0] n_long  [1..CAP+1] histogram by length  [256..256+CAP] cursors
-constexpr int TM_NLONG = 0, TM_HIST = 1, TM_CUR = 256, TM_WORDS = 512;
+constexpr int TM_NLONG = 0, TM_HIST = 1, TM_CUR = 256;      // TM_WORDS = 512: msm_sort_plan.hpp
 
 __global__ void task_count_kernel(const uint32_t* __restrict__ start, const uint32_t* __restrict__ end, uint32_t nb,
                                   uint32_t* __restrict__ tcount, uint32_t cap) {
@@ -804,10 +792,7 @@ __global__ void sched_check_kernel(const uint32_t* toff, const uint32_t* long_li
   }
 }
 
-static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, const uint64_t* scalars_dev, size_t n,
-                          bool montgomery, uint64_t* out_xyz_host, void* out_dev_xyzz, float* ms_accumulate,
-                          uint64_t* n_entries, int ws_idx, int sort_src, float* ms_scan, int l1_src = -1, int sets = 1,
-                          size_t set_stride = 0, size_t out_stride = 0);
+static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, const MsmJob& job);
 bool msm_sets_ok(zkp_ctx* ctx, uint64_t handle, int sets) {
   auto be = get_bases(ctx, handle);
   const zkp_tune& t = ctx->tune;
@@ -817,17 +802,9 @@ bool msm_sets_ok(zkp_ctx* ctx, uint64_t handle, int sets) {
   return sets >= 1 && sets <= 2 && (1 << lgs) == sets && !be->var && t.pair_top && t.pair_top_fuse_seg &&
          (t.sort_h1 <= 0 || t.sort_h1 >= lgs) && (double)be->n * be->W * sets < 2147483000.0;
 }
-void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scalars_dev, size_t n, bool montgomery,
-             uint64_t* out_xyz_host, void* out_dev_xyzz, float* ms_accumulate, uint64_t* n_entries, int ws_idx,
-             int sort_src, float* ms_scan, int l1_src, int sets, size_t set_stride, size_t out_stride) {
-  struct ChainReset {                // one-shot requests: never leak into a later MSM, whatever this call throws (bad handle, ...)
-    zkp_ctx* c;
-    ~ChainReset() {
-      c->msm_defer_reduce = false;
-      c->msm_acc_into = -1;
-    }
-  } chain_reset{ctx};
-  auto be = get_bases(ctx, handle);
+void msm_run(zkp_ctx* ctx, const MsmJob& job) {
+  auto be = get_bases(ctx, job.handle);
+  const size_t n = job.n;
   // Chunked MSM (round 4): a large MSM that runs on its own (Marlin's h_2 and opening witnesses: 6.3 M points) spent 3 ms in its
   // bucket sort — memory-bound kernels with the vector ALUs idle — before 5.6 ms of VALU-bound accumulation.  Split by index into
   // chunks that share ONE bucket array (bucket chaining: every chunk but the last defers the reduction, every chunk but the first
@@ -836,12 +813,11 @@ void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scala
   // ZKP_MSM_CHUNK=<points per chunk> (0 = off); not for MSMs that share a sort, belong to a sort group, are profiled, or are
   // part of a caller's own bucket chain.
   const size_t chunk_pts = (size_t)std::max<long long>(0, ctx->cfg.msm_chunk);        // zkp_ctx_config.msm_chunk_points / ZKP_MSM_CHUNK
-  const bool chunkable = chunk_pts >= 1024 && n >= 2 * chunk_pts && be->group == 1 && !be->var && sort_src < 0 && l1_src < 0 &&
-                         !be->group_flags && !ctx->profiling && !ms_accumulate && !ms_scan && !n_entries &&
-                         !ctx->msm_defer_reduce && ctx->msm_acc_into < 0 && ctx->msm_bucket_ws < 0 && !ctx->batch_mode && sets == 1;
+  const bool chunkable = chunk_pts >= 1024 && n >= 2 * chunk_pts && be->group == 1 && !be->var && job.sort_src < 0 && job.l1_src < 0 &&
+                         !be->group_flags && !ctx->profiling && !job.ms_accumulate && !job.ms_scan && !job.n_entries &&
+                         !job.defer_reduce && job.acc_into < 0 && job.bucket_ws < 0 && !ctx->batch_mode && job.sets == 1;
   if (!chunkable) {
-    msm_run_entry(ctx, be.get(), offset, scalars_dev, n, montgomery, out_xyz_host, out_dev_xyzz, ms_accumulate, n_entries,
-                  ws_idx, sort_src, ms_scan, l1_src, sets, set_stride, out_stride);
+    msm_run_entry(ctx, be.get(), job);
     return;
   }
   // (per is rounded up to a multiple of 256, so the chunk count is recomputed from it: with a ZKP_MSM_CHUNK that is not a multiple
@@ -856,7 +832,7 @@ void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scala
   const size_t rest = first && first < n ? n - first : n;
   const size_t nrest = (rest + per - 1) / per, per_rest = ((rest + nrest - 1) / nrest + 255) & ~(size_t)255;
   const size_t nch = (first && first < n ? 1 : 0) + (rest + per_rest - 1) / per_rest;
-  const int wa = ws_idx, wb = ws_idx ^ 2;                               // partner: 0 <-> 2, 1 <-> 3
+  const int wa = job.ws, wb = job.ws ^ 2;                               // partner: 0 <-> 2, 1 <-> 3
   hipStream_t sa = wa == 0 ? ctx->cur->stream : ctx->cur->ws[wa].stream, sb = wb == 0 ? ctx->cur->stream : ctx->cur->ws[wb].stream;
   // the partner's stream joins behind everything this MSM's stream has seen (scalars complete, bucket array of `wa` free)
   ZKP_HIP(hipEventRecord(ctx->cur->ws[wa].l1_done, sa));
@@ -865,12 +841,17 @@ void msm_run(zkp_ctx* ctx, uint64_t handle, size_t offset, const uint64_t* scala
   for (size_t k = 0; k < nch; k++) {
     const size_t len = std::min((k == 0 && first && first < n) ? first : per_rest, n - done);
     const bool last = k + 1 == nch;
-    const int w = ((nch - 1 - k) & 1) ? wb : wa;                        // the last chunk runs on `wa`: result, `done` event, read-back
-    ctx->msm_defer_reduce = !last;
-    ctx->msm_acc_into = k > 0 ? wa : -1;
-    ctx->msm_bucket_ws = wa;
-    msm_run_entry(ctx, be.get(), offset + done, scalars_dev + 4 * done, len, montgomery, last ? out_xyz_host : nullptr,
-                  last ? out_dev_xyzz : nullptr, nullptr, nullptr, w, -1, nullptr, -1);
+    MsmJob cj = job;                     // (chunkable: no sort sharing, no profiling outputs, one scalar vector)
+    cj.offset += done;
+    cj.scalars_dev += 4 * done;
+    cj.n = len;
+    cj.out_xyz_host = last ? job.out_xyz_host : nullptr;
+    cj.out_dev_xyzz = last ? job.out_dev_xyzz : nullptr;
+    cj.ws = ((nch - 1 - k) & 1) ? wb : wa;                              // the last chunk runs on `wa`: result, `done` event, read-back
+    cj.defer_reduce = !last;
+    cj.acc_into = k > 0 ? wa : -1;
+    cj.bucket_ws = wa;
+    msm_run_entry(ctx, be.get(), cj);
     done += len;
   }
   // the partner stream's last chunk was consumed by a later chunk on `sa` through the acc_done event; nothing of this MSM is left on `sb`
@@ -917,217 +898,246 @@ static VarPlan& var_plan(zkp_ctx* ctx, int c, int W, hipStream_t st) {
   return *vp;
 }
 
-static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, const uint64_t* scalars_dev, size_t n,
-                          bool montgomery, uint64_t* out_xyz_host, void* out_dev_xyzz, float* ms_accumulate,
-                          uint64_t* n_entries, int ws_idx, int sort_src, float* ms_scan, int l1_src, int sets, size_t set_stride,
-                          size_t out_stride) {
-  // sets > 1 (a power of two): ONE kernel chain for `sets` independent MSMs over the same bases — scalar vector g starts
-  // set_stride scalars behind vector g - 1, its XYZZ result goes out_stride bytes behind that of g - 1 and its Jacobian 3 fN words
-  // behind it in the workspace's `out`.  The proof index is one more set dimension on top of the window groups (lgk): bucket id =
-  // (g << (c - 1 + lgk)) | (set << (c - 1)) | key.  Everything from level 2 of the sort to `combine` sees sets * nb buckets; the
-  // reduction yields one result per vector.  Fixed-base plan with the fused pyramid top only (msm_sets_ok).
-  int lgs = 0;
-  while ((1 << lgs) < sets) lgs++;
-  ZKP_REQUIRE(sets == 1 || sets == 2, ZKP_ERR_BAD_ARG);        // the index arithmetic is written for 2^lgs sets; only 1 and 2 are tested
-  ZKP_REQUIRE(sets == 1 || (!be->var && !out_xyz_host && ctx->tune.pair_top && ctx->tune.pair_top_fuse_seg), ZKP_ERR_BAD_ARG);
-  const uint32_t S = (uint32_t)sets;
-  const MsmVtbl* vt = be->vt;
-  MsmWorkspace& ws = ctx->cur->ws[ws_idx];
-  // bucket chaining (ctx.hpp): one-shot requests, consumed by this MSM
-  const bool defer = ctx->msm_defer_reduce;
-  const int into = ctx->msm_acc_into;
-  const int bucket_ws = into >= 0 ? into : ctx->msm_bucket_ws;
-  ctx->msm_defer_reduce = false;
-  ctx->msm_acc_into = -1;
-  ctx->msm_bucket_ws = -1;
-  ZKP_REQUIRE(!(defer || into >= 0) || (n > 0 && !be->var && be->group == 1), ZKP_ERR_BAD_ARG);   // G1 only (msm_acc.hip)
-  // sort_src: workspace whose sorted entries + task schedule this MSM reuses (same scalars, window configuration and identity
-  // pattern); sort_src == ws_idx = the MSM that ran on this workspace just before (A -> L on one stream)
-  const bool reuse = sort_src >= 0;
-  MsmWorkspace& sw = reuse ? ctx->cur->ws[sort_src] : ws;          // owner of the sorted entries and the task schedule
-  hipStream_t st = ws_idx == 0 ? ctx->cur->stream : ws.stream;
-  const size_t XB = vt->bucket_bytes;                                // buckets, partial sums, pyramid levels
-  const size_t jac_words = 3 * (size_t)vt->fN;
-  uint32_t* out_jac = ws.out.as<uint32_t>((size_t)64 * 4 * S);
-  if (ms_accumulate) *ms_accumulate = 0.f;
-  if (ms_scan) *ms_scan = 0.f;
-  if (n_entries) *n_entries = 0;
-  if (n == 0) {
-    vt->write_identity(st, (char*)out_dev_xyzz, out_jac, S, out_stride, (uint32_t)jac_words);
-  } else {
-    const int c = be->c, W = be->W, wide = be->wide;
-    const int var = be->var ? 1 : 0;
-    const int lgk = be->lgk, K = 1 << lgk;                             // bucket sets (window groups, BasesEntry::lgk)
-    ZKP_REQUIRE(var == (lgk > 0), ZKP_ERR_BAD_ARG);
-    const uint32_t nb_w = 1u << (c - 1);                               // buckets of one window (digit range)
-    const int kbits = (c - 1) + lgk + lgs;                             // bits of a bucket id
-    const uint32_t nb = 1u << kbits;                                   // all buckets (of all scalar vectors)
-    const uint32_t nb_set = nb >> lgs;                                 // buckets of one scalar vector
-    const size_t E = n * (size_t)W * S;
-    ZKP_REQUIRE(E < 2147483000ull, ZKP_ERR_BAD_ARG);
+// ------------------------------------------------------------------------------------------- one MSM, phase by phase
+// Second stage of the fixed-base reduction's segmented sums: one block per level.  Levels below l_top sum the first stage's
+// partials (set g's follow those of set g - 1); from l_top on — the levels the fused top produced — the level's odd entries
+// themselves, straight from the pyramid.  l_top < 0: no fused top, every level has partials.
+static SegPlan stage_two_plan(const SegPlan& plan, int l_top) {
+  const int L = plan.L, l_part = l_top < 0 ? L : l_top;
+  SegPlan p2{};
+  p2.L = L;
+  p2.chunk = plan.chunk;
+  for (int l = 0; l < L; l++) {
+    p2.first_block[l] = l;
+    if (l < l_part) {
+      p2.off[l] = plan.first_block[l];
+      p2.stride[l] = 1;
+      p2.count[l] = plan.first_block[l + 1] - plan.first_block[l];
+      p2.set_step[l] = l_top < 0 ? 0 : plan.first_block[l_top];
+    } else {
+      p2.off[l] = plan.off[l];
+      p2.stride[l] = plan.stride[l];
+      p2.count[l] = plan.count[l];
+      p2.set_step[l] = plan.set_step[l];
+    }
+    ZKP_REQUIRE(p2.count[l] <= plan.chunk, ZKP_ERR_BAD_ARG);
+  }
+  p2.first_block[L] = L;
+  return p2;
+}
+
+// One MSM on its way through msm_run_entry: the request, who owns which intermediate result and — for n > 0 — the geometry and
+// the device arrays of its sort, task schedule and buckets.  Built once per MSM on the stack; msm_run_entry calls the phases in
+// the order they stand here.
+struct MsmRun {
+  zkp_ctx* ctx;
+  const MsmJob& job;
+  const BasesEntry* be;
+  const MsmVtbl* vt;
+  hipStream_t st;
+  // this MSM's own scratch, and the owners of the sorted entries + task schedule (job.sort_src), of the level-1 output (job.l1_src)
+  // and of the bucket array (job.acc_into / job.bucket_ws): each is `ws` unless the job names another workspace of the lane
+  MsmWorkspace *ws, *sw, *lw, *bws;
+  bool reuse, l1_reuse;            // the sort + schedule / only the level-1 output are another MSM's
+  uint32_t S;                      // scalar vectors (job.sets)
+  size_t XB, jac_words;            // bytes of a bucket / partial sum / pyramid point; 32-bit words of a Jacobian result
+  uint32_t* out_jac;
+  // n > 0 (plan)
+  uint32_t nb_w, nb, nb_set;       // buckets of one window (digit range), of all scalar vectors, of one scalar vector
+  size_t E;                        // nominal entries: scalars x windows x vectors
+  SortPlan sp;
+  SchedLayout sl;
+  uint64_t* kv;                    // level-1 output: (low key, val) pairs
+  uint32_t* vals;                  // values grouped by bucket (level-2 output)
+  uint32_t *hist, *offs;           // (bin, tile) counts and their exclusive scan
+  uint32_t *start, *end;           // of every bucket's run in `vals`
+  uint32_t *tcount, *toff, *task_start, *task_len, *task_dst, *long_list, *tmeta;   // the task schedule (sl)
+  uint4* desc;                     // task descriptors in the order the accumulate kernel walks them
+  const uint8_t *scan_inf, *grp;   // identity flags the digit scan uses; group bits of a shared level-1 pass
+  char *buckets, *task_partial;
+  uint32_t init;                   // 1: accumulate on top of the buckets that are there (job.acc_into)
+
+  // Argument checks and what an empty MSM needs as well.
+  // sets > 1 (MsmJob; a power of two): the Jacobian result of vector g lies 3 fN words behind that of g - 1 in the workspace's
+  // `out`.  The proof index is one more set dimension on top of the window groups (lgk): bucket id = (g << (c - 1 + lgk)) |
+  // (set << (c - 1)) | key.  Everything from level 2 of the sort to `combine` sees sets * nb buckets; the reduction yields one
+  // result per vector.  Fixed-base plan with the fused pyramid top only (msm_sets_ok).
+  void open() {
+    ZKP_REQUIRE(job.sets == 1 || job.sets == 2, ZKP_ERR_BAD_ARG);        // the index arithmetic is written for 2^lgs sets; only 1 and 2 are tested
+    ZKP_REQUIRE(job.sets == 1 || (!be->var && !job.out_xyz_host && ctx->tune.pair_top && ctx->tune.pair_top_fuse_seg), ZKP_ERR_BAD_ARG);
+    // bucket chaining (MsmJob): G1 only (msm_acc.hip)
+    ZKP_REQUIRE(!(job.defer_reduce || job.acc_into >= 0) || (job.n > 0 && !be->var && be->group == 1), ZKP_ERR_BAD_ARG);
+    MsmWorkspace* all = ctx->cur->ws;
+    const int bucket_ws = job.acc_into >= 0 ? job.acc_into : job.bucket_ws;
+    ws = &all[job.ws];
+    bws = bucket_ws >= 0 ? &all[bucket_ws] : ws;
+    // sort_src: workspace whose sorted entries + task schedule this MSM reuses (same scalars, window configuration and identity
+    // pattern); sort_src == ws = the MSM that ran on this workspace just before (A -> L on one stream)
+    reuse = job.sort_src >= 0;
+    sw = reuse ? &all[job.sort_src] : ws;
     // l1_src >= 0 (and no full reuse): the level-1 pass over these scalars — digit scan, (bin, tile) counts, scatter into bins —
     // was run by workspace l1_src of this lane for a GROUP of queries (it dropped only the bases that are the identity in all of
     // them); this MSM runs its own level 2 on that list and drops its own identities there (BasesEntry::filter_bit).
-    // l1_src == ws_idx: by the MSM that ran on this workspace just before.
-    const bool l1_reuse = !reuse && l1_src >= 0;
-    MsmWorkspace& lw = l1_reuse ? ctx->cur->ws[l1_src] : sw;           // owner of the level-1 output
-    uint32_t* vals = sw.vals.as<uint32_t>(E + 8);                    // + 8: the accumulate kernel reads aligned groups of eight                        // values grouped by bucket (level-2 output)
-    uint64_t* kv = lw.keys2.as<uint64_t>(E);                         // level-1 output: (low key, val) pairs
-    const uint32_t* sc = reinterpret_cast<const uint32_t*>(scalars_dev);
-    const int mont = montgomery ? 1 : 0;
-    // K6: group entries by bucket (two-level counting sort); sorted values land back in `vals`
-    // level-1 bins: enough of them that a bin (E / bins entries on average) fits the level-2 kernel's LDS stage; tiles:
-    // 2048 scalars, more for large MSMs so that the (bin x tile) count matrix stays small
-    const zkp_tune& tune = ctx->tune;
-    const int h1_env = tune.sort_h1;
-    int H1 = 10;
-    while (H1 < SORT_H1_MAX && (E >> H1) > SORT_BIN_TARGET) H1++;
-    if (h1_env > 0) H1 = std::min(SORT_H1_MAX, h1_env);
-    H1 = std::min(H1, kbits);
-    if (kbits - H1 > SORT_L_MAX) H1 = kbits - SORT_L_MAX;
-    ZKP_REQUIRE(H1 >= lgs, ZKP_ERR_BAD_ARG);                           // a level-1 bin never straddles two scalar vectors
-    const int LB = kbits - H1;                                         // low bits per level-1 bin
-    const uint32_t nbins1 = 1u << H1;
-    const uint32_t nbins_set = nbins1 >> lgs;                          // level-1 bins of one scalar vector (what the level-1 kernels see)
-    const size_t set_words = set_stride * 8;
-    uint32_t tile = SORT_SCALARS;
-    while ((n + tile - 1) / tile > 1536) tile += 256;
-    const uint32_t nblocks = (uint32_t)((n + tile - 1) / tile);
-    const size_t hist_n = (size_t)nbins1 * nblocks + 1;                // + total (== number of non-zero digits)
-    uint32_t* hist = lw.sort_tmp.as<uint32_t>(2 * hist_n);
-    uint32_t* offs = hist + hist_n;
-    uint32_t* start = sw.offsets.as<uint32_t>(2 * (size_t)nb);
-    uint32_t* end = start + nb;
+    // l1_src == ws: by the MSM that ran on this workspace just before.
+    l1_reuse = !reuse && job.l1_src >= 0;
+    lw = l1_reuse ? &all[job.l1_src] : sw;
+    st = job.ws == 0 ? ctx->cur->stream : ws->stream;
+    S = (uint32_t)job.sets;
+    XB = vt->bucket_bytes;
+    jac_words = 3 * (size_t)vt->fN;
+    out_jac = ws->out.as<uint32_t>((size_t)64 * 4 * S);
+    if (job.ms_accumulate) *job.ms_accumulate = 0.f;
+    if (job.ms_scan) *job.ms_scan = 0.f;
+    if (job.n_entries) *job.n_entries = 0;
+  }
+  void write_identity() { vt->write_identity(st, (char*)job.out_dev_xyzz, out_jac, S, job.out_stride, (uint32_t)jac_words); }
+
+  // n > 0: sizes, the geometry of the sort and of the schedule (msm_sort_plan.hpp) and the device arrays they describe
+  void plan() {
+    const int lgk = be->lgk;                                           // bucket sets (window groups, BasesEntry::lgk)
+    ZKP_REQUIRE(be->var == (lgk > 0), ZKP_ERR_BAD_ARG);
+    int lgs = 0;
+    while ((1u << lgs) < S) lgs++;
+    const int kbits = (be->c - 1) + lgk + lgs;                         // bits of a bucket id
+    nb_w = 1u << (be->c - 1);
+    nb = 1u << kbits;
+    nb_set = nb >> lgs;
+    E = job.n * (size_t)be->W * S;
+    ZKP_REQUIRE(E < 2147483000ull, ZKP_ERR_BAD_ARG);
+    vals = sw->vals.as<uint32_t>(E + 8);                               // + 8: the accumulate kernel reads aligned groups of eight
+    kv = lw->keys2.as<uint64_t>(E);
+    sp = sort_plan(job.n, be->W, job.sets, kbits, ctx->tune.sort_h1, ctx->tune.sort_staged);
+    ZKP_REQUIRE(sp.ok, ZKP_ERR_BAD_ARG);                               // a level-1 bin never straddles two scalar vectors
+    hist = lw->sort_tmp.as<uint32_t>(2 * sp.hist_n);
+    offs = hist + sp.hist_n;
+    start = sw->offsets.as<uint32_t>(2 * (size_t)nb);
+    end = start + nb;
     // see BasesEntry::sort_inf; a profiled (stand-alone, timed) MSM scans with its own flags so that its entry count is exact
-    const uint8_t* scan_inf = be->sort_inf && !ctx->profiling ? be->sort_inf : be->inf;
-    if (reuse) {
-      if (sort_src != ws_idx) ZKP_HIP(hipStreamWaitEvent(st, sw.sorted, 0));
-    } else if (l1_reuse) {
-      if (l1_src != ws_idx) ZKP_HIP(hipStreamWaitEvent(st, lw.l1_done, 0));
+    scan_inf = be->sort_inf && !ctx->profiling ? be->sort_inf : be->inf;
+    grp = scan_inf == be->sort_inf ? be->group_flags : nullptr;        // group bits only with the group's scan flags
+    sl = sched_layout(nb, E, be->cap);
+    tcount = sw->sched.as<uint32_t>(sl.words);                         // (a device allocation: 256-byte aligned)
+    toff = tcount + sl.toff;
+    task_start = tcount + sl.task_start;
+    task_len = tcount + sl.task_len;
+    task_dst = tcount + sl.task_dst;
+    long_list = tcount + sl.long_list;
+    tmeta = tcount + sl.tmeta;
+    desc = reinterpret_cast<uint4*>(reinterpret_cast<char*>(tcount) + sl.desc_bytes);
+    // level l of the reduction pyramid lives at element offset lvl_off[l] of `buckets` (level 0 = buckets); all-zero bytes are a
+    // valid identity (zz == 0), so empty buckets need no kernel
+    buckets = reinterpret_cast<char*>(bws->buckets.get((size_t)2 * nb * XB + XB));
+    task_partial = reinterpret_cast<char*>(ws->partial.get((size_t)sl.max_tasks * XB));
+    init = job.acc_into >= 0 ? 1u : 0u;
+  }
+
+  // threads per workgroup of a level-1 pass (tune.sort_nt_hist / sort_nt_scatter: 1024, 512 or 256) as a compile-time constant
+  // (A/B: ZKP_SORT_NT_HIST / ZKP_SORT_NT_SCATTER = 256 restores rounds 3-5)
+  template <class F>
+  static void with_sort_nt(int nt, F&& f) {
+    if (nt >= 1024) f(std::integral_constant<int, 1024>{});
+    else if (nt >= 512) f(std::integral_constant<int, 512>{});
+    else f(std::integral_constant<int, 256>{});
+  }
+  // K5 + level 1 of K6: histogram pass, scan of the (bin, tile) counts, scatter pass into the level-1 bins
+  template <class FrP>
+  void sort_level1_launch() {
+    const uint32_t* sc = reinterpret_cast<const uint32_t*>(job.scalars_dev);
+    const size_t n = job.n, offset = job.offset, set_words = job.set_stride * 8;
+    const int mont = job.montgomery ? 1 : 0, c = be->c, W = be->W, wide = be->wide, lgk = be->lgk;
+    with_sort_nt(ctx->tune.sort_nt_hist, [&](auto nt) {
+      constexpr int NT = decltype(nt)::value;
+      hipLaunchKernelGGL((sort_hist_kernel<FrP, NT>), dim3(sp.nblocks, S), dim3(NT), 0, st, sc, n, offset, scan_inf, mont, c, W, wide, nb_w,
+                         sp.LB, sp.nbins_set, hist, sp.nblocks, sp.tile, lgk, set_words);
+    });
+    exclusive_scan_u32(st, hist, offs, sp.hist_n, ws->scan_tmp);
+    if (sp.staged_sub) {
+      with_sort_nt(ctx->tune.sort_nt_scatter, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((sort_scatter_staged_kernel<FrP, NT>), dim3(sp.nblocks, S), dim3(NT), sp.staged_lds, st, sc, n, offset, scan_inf,
+                           mont, be->n, c, W, wide, nb_w, sp.LB, sp.nbins_set, offs, sp.nblocks, sp.tile, kv, lgk, grp, sp.staged_sub,
+                           set_words);
+      });
     } else {
-      ZKP_HIP(hipMemsetAsync(hist + hist_n - 1, 0, 4, st));
+      hipLaunchKernelGGL(sort_scatter_kernel<FrP>, dim3(sp.nblocks, S), dim3(256), 0, st, sc, n, offset, scan_inf, mont, be->n, c, W, wide,
+                         nb_w, sp.LB, sp.nbins_set, offs, sp.nblocks, sp.tile, kv, lgk, grp, set_words);
     }
-    const uint8_t* grp = scan_inf == be->sort_inf ? be->group_flags : nullptr;   // group bits only with the group's scan flags
-    // staged level-1 scatter (sort_scatter_staged_kernel): sub-rounds of `staged_sub` scalars whose entries fit the LDS stage;
-    // not for > 2048 level-1 bins (the two counter arrays would leave one workgroup per CU) or very narrow windows
-    uint32_t staged_sub = 0;
-    size_t staged_lds = 0;
-    if (tune.sort_staged && nbins_set <= 2048 && (size_t)256 * W * 8 <= SORT_STAGE_BYTES) {
-      staged_sub = (uint32_t)(SORT_STAGE_BYTES / ((size_t)W * 8)) / 256 * 256;
-      staged_sub = std::min<uint32_t>(staged_sub, tile);
-      staged_lds = ((size_t)nbins_set + ((nbins_set + 3) & ~3u)) * 4 + (size_t)staged_sub * W * 8;
-    }
-    const bool timed_scan = ms_scan && ctx->profiling && !reuse && !l1_reuse;      // K5 "scalar scan": histogram pass + count scan + scatter pass
+  }
+  void sort_level1() {
+    ZKP_HIP(hipMemsetAsync(hist + sp.hist_n - 1, 0, 4, st));
+    const bool timed_scan = job.ms_scan && ctx->profiling;          // K5 "scalar scan": histogram pass + count scan + scatter pass
     if (timed_scan) ZKP_HIP(hipEventRecord(ctx->ev2, st));
-    if (reuse || l1_reuse) {
-    } else {
-      // threads per workgroup of the two level-1 passes (A/B: ZKP_SORT_NT_HIST / ZKP_SORT_NT_SCATTER = 256 restores rounds 3-5)
-      const int nt_hist = tune.sort_nt_hist, nt_scat = tune.sort_nt_scatter;       // each 1024, 512 or 256
-      auto level1 = [&](auto tag) {
-        using FrP = decltype(tag);
-        auto hist_l = [&](auto nt) {
-          constexpr int NT = decltype(nt)::value;
-          hipLaunchKernelGGL((sort_hist_kernel<FrP, NT>), dim3(nblocks, S), dim3(NT), 0, st, sc, n, offset, scan_inf, mont, c, W, wide, nb_w,
-                             LB, nbins_set, hist, nblocks, tile, lgk, set_words);
-        };
-        if (nt_hist >= 1024) hist_l(std::integral_constant<int, 1024>{});
-        else if (nt_hist >= 512) hist_l(std::integral_constant<int, 512>{});
-        else hist_l(std::integral_constant<int, 256>{});
-        exclusive_scan_u32(st, hist, offs, hist_n, ws.scan_tmp);
-        if (staged_sub) {
-          auto scat_l = [&](auto nt) {
-            constexpr int NT = decltype(nt)::value;
-            hipLaunchKernelGGL((sort_scatter_staged_kernel<FrP, NT>), dim3(nblocks, S), dim3(NT), staged_lds, st, sc, n, offset,
-                               scan_inf, mont, be->n, c, W, wide, nb_w, LB, nbins_set, offs, nblocks, tile, kv, lgk, grp, staged_sub,
-                               set_words);
-          };
-          if (nt_scat >= 1024) scat_l(std::integral_constant<int, 1024>{});
-          else if (nt_scat >= 512) scat_l(std::integral_constant<int, 512>{});
-          else scat_l(std::integral_constant<int, 256>{});
-        } else {
-          hipLaunchKernelGGL(sort_scatter_kernel<FrP>, dim3(nblocks, S), dim3(256), 0, st, sc, n, offset, scan_inf, mont, be->n, c, W, wide,
-                             nb_w, LB, nbins_set, offs, nblocks, tile, kv, lgk, grp, set_words);
-        }
-      };
-      if (be->curve == ZKP_BN254) level1(Bn254Fr{});
-      else level1(Bls381Fr{});
-    }
+    if (be->curve == ZKP_BN254) sort_level1_launch<Bn254Fr>();
+    else sort_level1_launch<Bls381Fr>();
     if (timed_scan) {
       ZKP_HIP(hipEventRecord(ctx->ev3, st));
       ZKP_HIP(hipEventSynchronize(ctx->ev3));
-      ZKP_HIP(hipEventElapsedTime(ms_scan, ctx->ev2, ctx->ev3));
+      ZKP_HIP(hipEventElapsedTime(job.ms_scan, ctx->ev2, ctx->ev3));
     }
-    if (!reuse && !l1_reuse) ZKP_HIP(hipEventRecord(ws.l1_done, st));
-    if (!reuse && !l1_reuse) ctx->mark(st, ":l1");
-    if (!reuse)
-      hipLaunchKernelGGL(sort_bin_kernel, dim3(nbins1), dim3(SORT_BIN_THREADS), ((size_t)4 << LB) + 4 * (size_t)SORT_BIN_STAGE, st,
-                         kv, offs, nblocks, LB, vals, start, end, (l1_reuse || grp) ? be->filter_bit : -1);
-    uint32_t* const sorted_vals = vals;
-    // K7 scheduling: buckets -> tasks (<= CAP entries), ordered by length
-    const uint32_t max_tasks = nb + (uint32_t)(E / be->cap) + 1;
-    uint32_t* sched = sw.sched.as<uint32_t>((size_t)2 * (nb + 2) + (size_t)8 * max_tasks + TM_WORDS + 8);
-    uint32_t* tcount = sched;                       // nb + 1
-    uint32_t* toff = tcount + (nb + 2);             // nb + 1  (toff[nb] = number of tasks)
-    uint32_t* task_start = toff + (nb + 2);
-    uint32_t* task_len = task_start + max_tasks;
-    uint32_t* task_dst = task_len + max_tasks;
-    uint32_t* long_list = task_dst + max_tasks;
-    uint32_t* tmeta = long_list + max_tasks;
-    uint4* desc = reinterpret_cast<uint4*>((reinterpret_cast<uintptr_t>(tmeta + TM_WORDS) + 15) & ~(uintptr_t)15);   // max_tasks x 16 B
-    if (!reuse) {
-      ZKP_HIP(hipMemsetAsync(tmeta, 0, TM_WORDS * 4, st));
-      hipLaunchKernelGGL(task_count_kernel, dim3((nb + 256) / 256), dim3(256), 0, st, start, end, nb, tcount, be->cap);
-      exclusive_scan_u32(st, tcount, toff, (size_t)nb + 1, ws.scan_tmp2);
-      // (1024 threads per workgroup since round 6: a quarter of the per-(block, length) global atomics on the 129 length counters)
-      const uint32_t tnt = (uint32_t)tune.task_nt;                    // ZKP_TASK_NT: 1024, 512 or 256
-      hipLaunchKernelGGL(task_fill_kernel, dim3((nb + tnt - 1) / tnt), dim3(tnt), 0, st, start, end, toff, nb, task_start,
-                         task_len, task_dst, long_list, tmeta, be->cap);
-      hipLaunchKernelGGL(task_cursor_kernel, dim3(1), dim3(64), 0, st, tmeta);
-      hipLaunchKernelGGL(task_order_kernel, dim3((max_tasks + tnt - 1) / tnt), dim3(tnt), 0, st, task_start, task_len, task_dst,
-                         toff + nb, tmeta, desc);
-      ZKP_HIP(hipEventRecord(ws.sorted, st));
-      ctx->mark(st, ":sorted");
-    }
-    // level l of the reduction pyramid lives at element offset lvl_off[l] of `buckets` (level 0 = buckets);
-    // all-zero bytes are a valid identity (zz == 0), so empty buckets need no kernel
-    // (into >= 0: the bucket array of workspace `into`, which holds the finished buckets of an MSM over the same bucket range;
-    //  its accumulate + combine must be complete before this one's start)
-    MsmWorkspace& bws = bucket_ws >= 0 ? ctx->cur->ws[bucket_ws] : ws;
-    char* buckets = reinterpret_cast<char*>(bws.buckets.get((size_t)2 * nb * XB + XB));
-    char* task_partial = reinterpret_cast<char*>(ws.partial.get((size_t)max_tasks * XB));
-    const bool zero_all = tune.memset_buckets;                        // A/B: round-2 behaviour
-    const uint32_t init = into >= 0 ? 1u : 0u;
+    ZKP_HIP(hipEventRecord(ws->l1_done, st));
+    ctx->mark(st, ":l1");
+  }
+  // level 2 of K6: one workgroup per level-1 bin groups its entries by bucket; the sorted values land in `vals`
+  void sort_level2() {
+    hipLaunchKernelGGL(sort_bin_kernel, dim3(sp.nbins1), dim3(SORT_BIN_THREADS), sp.bin_lds, st, kv, offs, sp.nblocks, sp.LB, vals, start,
+                       end, (l1_reuse || grp) ? be->filter_bit : -1);
+  }
+  // K7 scheduling: buckets -> tasks (<= cap entries), ordered by length
+  void schedule_tasks() {
+    const uint32_t cap = be->cap, max_tasks = sl.max_tasks;
+    ZKP_HIP(hipMemsetAsync(tmeta, 0, TM_WORDS * 4, st));
+    hipLaunchKernelGGL(task_count_kernel, dim3((nb + 256) / 256), dim3(256), 0, st, start, end, nb, tcount, cap);
+    exclusive_scan_u32(st, tcount, toff, (size_t)nb + 1, ws->scan_tmp2);
+    // (1024 threads per workgroup since round 6: a quarter of the per-(block, length) global atomics on the 129 length counters)
+    const uint32_t tnt = (uint32_t)ctx->tune.task_nt;                  // ZKP_TASK_NT: 1024, 512 or 256
+    hipLaunchKernelGGL(task_fill_kernel, dim3((nb + tnt - 1) / tnt), dim3(tnt), 0, st, start, end, toff, nb, task_start, task_len,
+                       task_dst, long_list, tmeta, cap);
+    hipLaunchKernelGGL(task_cursor_kernel, dim3(1), dim3(64), 0, st, tmeta);
+    hipLaunchKernelGGL(task_order_kernel, dim3((max_tasks + tnt - 1) / tnt), dim3(tnt), 0, st, task_start, task_len, task_dst,
+                       toff + nb, tmeta, desc);
+    ZKP_HIP(hipEventRecord(ws->sorted, st));
+    ctx->mark(st, ":sorted");
+  }
+  // Chained (job.acc_into), the bucket array holds the finished buckets of an MSM over the same bucket range, whose accumulate +
+  // combine must be complete before this one's start; otherwise the empty buckets become the identity
+  void init_buckets() {
     if (init) {
-      ZKP_REQUIRE(bws.chain_nb == nb && bws.chain_xb == XB, ZKP_ERR_BAD_ARG);
-      ZKP_HIP(hipStreamWaitEvent(st, bws.acc_done, 0));        // (recorded on whichever stream ran the MSM that filled them)
-    } else if (zero_all) ZKP_HIP(hipMemsetAsync(buckets, 0, (size_t)nb * XB, st));
+      ZKP_REQUIRE(bws->chain_nb == nb && bws->chain_xb == XB, ZKP_ERR_BAD_ARG);
+      ZKP_HIP(hipStreamWaitEvent(st, bws->acc_done, 0));        // (recorded on whichever stream ran the MSM that filled them)
+    } else if (ctx->tune.memset_buckets) ZKP_HIP(hipMemsetAsync(buckets, 0, (size_t)nb * XB, st));        // A/B: round-2 behaviour
     else hipLaunchKernelGGL(zero_empty_buckets_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, start, end, nb, buckets, (uint32_t)XB);
-    bws.chain_nb = 0;
-    const bool timed = ms_accumulate && ctx->profiling;
+    bws->chain_nb = 0;
+  }
+  // K7: one lane per task; with ZKP_DEBUG_MSM a consistency check of the schedule behind it
+  void accumulate() {
+    uint32_t* redo = ws->redo.as<uint32_t>((size_t)sl.max_tasks + 1);
+    const bool timed = job.ms_accumulate && ctx->profiling;
     if (timed) ZKP_HIP(hipEventRecord(ctx->ev2, st));
-    const uint32_t force_redo = tune.debug_force_redo ? 2u : 0u;      // tests
+    const uint32_t force_redo = ctx->tune.debug_force_redo ? 2u : 0u;      // tests
     ctx->mark(st, ":acc0");
-    vt->accumulate(st, tune, be->table, sorted_vals, desc, toff + nb, max_tasks, buckets, task_partial,
-                   ws.redo.as<uint32_t>((size_t)max_tasks + 1), init | force_redo);
+    vt->accumulate(st, ctx->tune, be->table, vals, desc, toff + nb, sl.max_tasks, buckets, task_partial, redo, init | force_redo);
     ctx->mark(st, ":acc1");
     if (timed) {
       ZKP_HIP(hipEventRecord(ctx->ev3, st));
       ZKP_HIP(hipEventSynchronize(ctx->ev3));
-      ZKP_HIP(hipEventElapsedTime(ms_accumulate, ctx->ev2, ctx->ev3));
+      ZKP_HIP(hipEventElapsedTime(job.ms_accumulate, ctx->ev2, ctx->ev3));
     }
-    const int dbg = tune.debug_msm;
-    if (dbg) {
-      uint32_t* rep = ws.redo.as<uint32_t>((size_t)max_tasks + 1);     // accumulate is done with it
+    if (ctx->tune.debug_msm) {
+      uint32_t* rep = redo;                                              // accumulate is done with it
       ZKP_HIP(hipStreamSynchronize(st));
       ZKP_HIP(hipMemsetAsync(rep, 0, 32, st));
-      hipLaunchKernelGGL(sched_check_kernel, dim3(256), dim3(256), 0, st, toff, long_list, tmeta, nb, max_tasks, rep);
+      hipLaunchKernelGGL(sched_check_kernel, dim3(256), dim3(256), 0, st, toff, long_list, tmeta, nb, sl.max_tasks, rep);
       uint32_t h[8];
       ZKP_HIP(hipMemcpyAsync(h, rep, 32, hipMemcpyDeviceToHost, st));
       ZKP_HIP(hipStreamSynchronize(st));
       printf("[msm] group=%d n=%zu nb=%u max_tasks=%u: toff inversions=%u max tasks/bucket=%u bad long_list=%u n_long=%u n_tasks=%u overflow=%u\n",
-             be->group, n, nb, max_tasks, h[0], h[1], h[2], h[3], h[4], h[5]);
+             be->group, job.n, nb, sl.max_tasks, h[0], h[1], h[2], h[3], h[4], h[5]);
       fflush(stdout);
     }
+  }
+  // the partial sums of the buckets that were split into several tasks -> their buckets; then the entry count, if asked for
+  void combine() {
+    const int dbg = ctx->tune.debug_msm;
 #ifdef ZKP_ABLATION   // ZKP_DEBUG_MSM=2 skips the combine step (wrong buckets): ablation builds only
     if (dbg != 2)
 #endif
@@ -1137,71 +1147,63 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
       printf("[msm] combine: %s\n", hipGetErrorString(e));
       fflush(stdout);
     }
-    if (n_entries) {
-      *n_entries = E;                                   // nominal: scalars x windows
+    if (job.n_entries) {
+      *job.n_entries = E;                               // nominal: scalars x windows
       if (ctx->profiling) {                             // exact: what the scan emitted (identity bases / zero digits dropped)
         uint32_t emitted = 0;
-        ZKP_HIP(hipMemcpyAsync(&emitted, offs + hist_n - 1, 4, hipMemcpyDeviceToHost, st));
+        ZKP_HIP(hipMemcpyAsync(&emitted, offs + sp.hist_n - 1, 4, hipMemcpyDeviceToHost, st));
         ZKP_HIP(hipStreamSynchronize(st));
-        *n_entries = emitted;
+        *job.n_entries = emitted;
       }
     }
-    if (var) {
-      // K8, variable-base: the pairwise pyramid runs over all W bucket sets at once (pairs never straddle windows), c - 1
-      // levels deep; two descriptor-driven segmented sums give R_t; 256 lanes weigh them by 2^t (<= 255 doublings each)
-      VarPlan& vp = var_plan(ctx, c, K, st);
-      uint32_t lvl_off = 0, cnt = nb;
-      for (int l = 0; l < c - 1; l++) {
-        vt->pair(st, buckets + (size_t)lvl_off * XB, buckets + (size_t)(lvl_off + cnt) * XB, cnt / 2);
-        lvl_off += cnt;
-        cnt /= 2;
-      }
-      const char* roots = buckets + (size_t)lvl_off * XB;            // cnt == K (one root per bucket set)
-      char* partial = reinterpret_cast<char*>(ws.tmp.get(((size_t)vp.n1 + 256 + 8) * XB));
-      char* R = partial + (size_t)vp.n1 * XB;
-      vt->segsum_desc(st, buckets, vp.d1.as<SegDesc>(vp.n1), vp.n1, partial);
-      vt->segsum_desc(st, partial, vp.d2.as<SegDesc>(256), 256, R);
-      vt->final_var(st, R, roots, c, K, (char*)out_dev_xyzz, out_jac);
-      ZKP_HIP(hipGetLastError());
-      if (out_xyz_host) {
-        ZKP_HIP(hipMemcpyAsync(out_xyz_host, out_jac, jac_words * 4, hipMemcpyDeviceToHost, st));
-        ZKP_HIP(hipStreamSynchronize(st));
-      }
-      return;
+  }
+  // K8, variable-base: the pairwise pyramid runs over all K bucket sets at once (pairs never straddle windows), c - 1 levels
+  // deep; two descriptor-driven segmented sums give R_t; 256 lanes weigh them by 2^t (<= 255 doublings each)
+  void reduce_var() {
+    const int c = be->c, K = 1 << be->lgk;
+    VarPlan& vp = var_plan(ctx, c, K, st);
+    uint32_t lvl_off = 0, cnt = nb;
+    for (int l = 0; l < c - 1; l++) {
+      vt->pair(st, buckets + (size_t)lvl_off * XB, buckets + (size_t)(lvl_off + cnt) * XB, cnt / 2);
+      lvl_off += cnt;
+      cnt /= 2;
     }
-    if (defer) {
-      // the buckets stay as they are for the MSM that reduces them together with its own (msm_acc_into); this one contributes
-      // the identity to whatever sums the results
-      bws.chain_nb = nb;
-      bws.chain_xb = XB;
-      ZKP_HIP(hipEventRecord(bws.acc_done, st));
-      vt->write_identity(st, (char*)out_dev_xyzz, out_jac, S, out_stride, (uint32_t)jac_words);
-      ZKP_HIP(hipGetLastError());
-      ZKP_REQUIRE(!out_xyz_host, ZKP_ERR_BAD_ARG);
-      return;
-    }
-#ifdef ZKP_ABLATION
-    if (ctx->dbg_skip_k8) return;                  // ablation experiments only (wrong result)
-#endif
-    // K8: pyramid
-    const int L = c - 1;                           // levels with odd entries: 0..L-1 ; root = level L
+    const char* roots = buckets + (size_t)lvl_off * XB;            // cnt == K (one root per bucket set)
+    char* partial = reinterpret_cast<char*>(ws->tmp.get(((size_t)vp.n1 + 256 + 8) * XB));
+    char* R = partial + (size_t)vp.n1 * XB;
+    vt->segsum_desc(st, buckets, vp.d1.as<SegDesc>(vp.n1), vp.n1, partial);
+    vt->segsum_desc(st, partial, vp.d2.as<SegDesc>(256), 256, R);
+    vt->final_var(st, R, roots, c, K, (char*)job.out_dev_xyzz, out_jac);
+  }
+  // job.defer_reduce: the buckets stay as they are for the MSM that reduces them together with its own (acc_into); this one
+  // contributes the identity to whatever sums the results
+  void defer_buckets() {
+    bws->chain_nb = nb;
+    bws->chain_xb = XB;
+    ZKP_HIP(hipEventRecord(bws->acc_done, st));
+    write_identity();
+    ZKP_HIP(hipGetLastError());
+    ZKP_REQUIRE(!job.out_xyz_host, ZKP_ERR_BAD_ARG);
+  }
+  // K8, fixed-base: pairwise pyramid, O_l = sum of the odd entries of level l in two segmented-sum stages, result = sum_l 2^l O_l + root.
+  // Where the levels live: msm_pyramid.hpp (with S scalar vectors the sets lie side by side up to the level the fused top starts
+  // from; the top of set g then writes into a region of its own).  blocks, first_block, count: per set.
+  // Round 6: the one-workgroup top of the pyramid and the segmented sums of the levels below it run in ONE launch (msm_group.hip
+  // pair_top_segsum_kernel); the second stage then sums the partials of the low levels and, directly from the pyramid, the odd
+  // entries of the top's levels (<= PAIR_TOP_MAX / 2 = one block each).  ZKP_PAIR_TOP_FUSE_SEG=0: pair_top, then both stages (rounds 3-5).
+  // (ZKP_PAIR_TOP_MAX is rounded down to a power of two: the fused top starts at the level whose size EQUALS top_max)
+  void reduce_fixed() {
+    const zkp_tune& tune = ctx->tune;
+    const int L = be->c - 1;                         // levels with odd entries: 0..L-1 ; root = level L
     SegPlan plan{};
     plan.L = L;
     const uint32_t chunk = ctx->batch_mode ? SEG_CHUNK_BATCH : SEG_CHUNK;
     plan.chunk = chunk;
-    // Where the levels live: msm_pyramid.hpp (with S scalar vectors the sets lie side by side up to the level the fused top starts
-    // from; the top of set g then writes into a region of its own).  blocks, first_block, count: per set.
-    // Round 6: the one-workgroup top of the pyramid and the segmented sums of the levels below it run in ONE launch (msm_group.hip
-    // pair_top_segsum_kernel); the second stage then sums the partials of the low levels and, directly from the pyramid, the odd
-    // entries of the top's levels (<= PAIR_TOP_MAX / 2 = one block each).  ZKP_PAIR_TOP_FUSE_SEG=0: pair_top, then both stages (rounds 3-5).
-    // (ZKP_PAIR_TOP_MAX is rounded down to a power of two: the fused top starts at the level whose size EQUALS top_max)
     const bool top_fused = tune.pair_top;
     const uint32_t top_max = (uint32_t)tune.pair_top_max;
     const PyramidLevels lv = pyramid_levels(nb_set, S, L, top_fused && tune.pair_top_fuse_seg, top_max, chunk);
-    ZKP_REQUIRE(lv.end <= 2 * nb, ZKP_ERR_BAD_ARG);       // the bucket buffer holds 2 nb + 1 points
+    ZKP_REQUIRE(lv.end <= 2 * nb, ZKP_ERR_BAD_ARG);         // the bucket buffer holds 2 nb + 1 points
     const int l_top = lv.l_top;                      // first level the fused top produces the successor of
-    char* const top_base = l_top >= 0 ? buckets + (size_t)lv.off[l_top] * XB : nullptr;
-    const uint32_t top_cnt = lv.top_cnt;
     uint32_t blocks = 0;
     for (int l = 0; l < L; l++) {
       const uint32_t lvl_off = lv.off[l], cnt = lv.cnt[l];
@@ -1220,56 +1222,65 @@ static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, size_t offset, con
     plan.first_block[L] = blocks;
     const char* root = buckets + (size_t)lv.off[L] * XB;    // the root of set g lies lv.step[L] entries further on
     ZKP_REQUIRE(S == 1 || (L > 0 && l_top >= 0), ZKP_ERR_BAD_ARG);
-    char* partial = reinterpret_cast<char*>(ws.tmp.get((size_t)S * ((size_t)blocks + 64) * XB));
+    char* partial = reinterpret_cast<char*>(ws->tmp.get((size_t)S * ((size_t)blocks + 64) * XB));
     char* Obuf = partial + (size_t)S * blocks * XB;        // L sums per set
     if (L > 0 && l_top >= 0) {
       SegPlan low = plan;                                    // levels 0 .. l_top - 1: complete before this launch
       low.L = l_top;
-      const uint32_t blocks_low = plan.first_block[l_top];
-      vt->pair_top_segsum(st, top_base, top_cnt, buckets, &low, partial, blocks_low, S);
-      SegPlan p2{};
-      p2.L = L;
-      p2.chunk = chunk;
-      for (int l = 0; l < L; l++) {
-        p2.first_block[l] = l;
-        if (l < l_top) {                                     // the level's partials
-          p2.off[l] = plan.first_block[l];
-          p2.stride[l] = 1;
-          p2.count[l] = plan.first_block[l + 1] - plan.first_block[l];
-          p2.set_step[l] = blocks_low;                       // set g's partials follow those of set g - 1
-        } else {                                             // the level's odd entries themselves
-          p2.off[l] = plan.off[l];
-          p2.stride[l] = plan.stride[l];
-          p2.count[l] = plan.count[l];
-          p2.set_step[l] = plan.set_step[l];
-        }
-        ZKP_REQUIRE(p2.count[l] <= chunk, ZKP_ERR_BAD_ARG);
-      }
-      p2.first_block[L] = L;
+      vt->pair_top_segsum(st, buckets + (size_t)lv.off[l_top] * XB, lv.top_cnt, buckets, &low, partial, plan.first_block[l_top], S);
+      const SegPlan p2 = stage_two_plan(plan, l_top);
       vt->segsum(st, partial, &p2, Obuf, L, buckets, l_top, S);
     } else if (L > 0) {
       vt->segsum(st, buckets, &plan, partial, blocks, nullptr, 1 << 30, 1);
-      SegPlan p2{};
-      p2.L = L;
-      p2.chunk = chunk;
-      for (int l = 0; l < L; l++) {
-        p2.first_block[l] = l;
-        p2.off[l] = plan.first_block[l];
-        p2.stride[l] = 1;
-        p2.count[l] = plan.first_block[l + 1] - plan.first_block[l];
-        ZKP_REQUIRE(p2.count[l] <= chunk, ZKP_ERR_BAD_ARG);
-      }
-      p2.first_block[L] = L;
+      const SegPlan p2 = stage_two_plan(plan, -1);
       vt->segsum(st, partial, &p2, Obuf, L, nullptr, 1 << 30, 1);
     }
-    vt->final(st, Obuf, L, root, (char*)out_dev_xyzz, out_jac, S, lv.step[L], out_stride, (uint32_t)jac_words);
+    vt->final(st, Obuf, L, root, (char*)job.out_dev_xyzz, out_jac, S, lv.step[L], job.out_stride, (uint32_t)jac_words);
     ctx->mark(st, ":reduced");
   }
-  ZKP_HIP(hipGetLastError());
-  if (out_xyz_host) {
-    ZKP_HIP(hipMemcpyAsync(out_xyz_host, out_jac, jac_words * 4, hipMemcpyDeviceToHost, st));
-    ZKP_HIP(hipStreamSynchronize(st));
+  // the Jacobian result -> host, if asked for (the only synchronisation of an MSM that is not profiled)
+  void read_back() {
+    ZKP_HIP(hipGetLastError());
+    if (job.out_xyz_host) {
+      ZKP_HIP(hipMemcpyAsync(job.out_xyz_host, out_jac, jac_words * 4, hipMemcpyDeviceToHost, st));
+      ZKP_HIP(hipStreamSynchronize(st));
+    }
   }
+};
+
+static void msm_run_entry(zkp_ctx* ctx, const BasesEntry* be, const MsmJob& job) {
+  MsmRun r{ctx, job, be, be->vt};
+  r.open();
+  if (job.n == 0) {
+    r.write_identity();
+    r.read_back();
+    return;
+  }
+  r.plan();
+  // K5 + K6 + K7 scheduling, or as much of them as another MSM over the same scalars has done already
+  if (r.reuse) {
+    if (job.sort_src != job.ws) ZKP_HIP(hipStreamWaitEvent(r.st, r.sw->sorted, 0));
+  } else {
+    if (!r.l1_reuse) r.sort_level1();
+    else if (job.l1_src != job.ws) ZKP_HIP(hipStreamWaitEvent(r.st, r.lw->l1_done, 0));
+    r.sort_level2();
+    r.schedule_tasks();
+  }
+  r.init_buckets();
+  r.accumulate();
+  r.combine();
+  if (be->var) {
+    r.reduce_var();
+  } else if (job.defer_reduce) {
+    r.defer_buckets();
+    return;
+  } else {
+#ifdef ZKP_ABLATION
+    if (ctx->dbg_skip_k8) return;                  // ablation experiments only (wrong result)
+#endif
+    r.reduce_fixed();
+  }
+  r.read_back();
 }
 
 // `count` MSMs against ONE resident base vector (different offsets / lengths / scalar vectors), three in flight at a
@@ -1316,7 +1327,14 @@ void msm_run_multi(zkp_ctx* ctx, size_t count, const uint64_t* handles, const si
     const size_t n = std::min(ns[k], be->n - offsets[k]);        // ark min(len) truncation
     ctx->cur = &ctx->lanes[li];
     ctx->cur_idx = li;
-    msm_run(ctx, handles[k], offsets[k], scalars_dev[k], n, montgomery, nullptr, nullptr, nullptr, nullptr, w);
+    MsmJob job;
+    job.handle = handles[k];
+    job.offset = offsets[k];
+    job.scalars_dev = scalars_dev[k];
+    job.n = n;
+    job.montgomery = montgomery;
+    job.ws = w;
+    msm_run(ctx, job);
     ZKP_HIP(hipMemcpyAsync(ctx->pinned + k * jw, ctx->lanes[li].ws[w].out.p, words * 4, hipMemcpyDeviceToHost, stream_of(li, w)));
   }
   ctx->cur = restore.cur;
@@ -1371,7 +1389,12 @@ void msm_var_run(zkp_ctx* ctx, int curve, int group, const uint64_t* xy_host, co
     sdev = ctx->msm_scalars.as<uint64_t>(n * 4);
     ZKP_HIP(hipMemcpyAsync(sdev, scalars_host, n * 32, hipMemcpyHostToDevice, st));
   }
-  msm_run_entry(ctx, &e, 0, sdev, n, montgomery, out_xyz_host, nullptr, nullptr, nullptr, 0, -1, nullptr);
+  MsmJob job;                                  // (no handle: the entry lives on this stack)
+  job.scalars_dev = sdev;
+  job.n = n;
+  job.montgomery = montgomery;
+  job.out_xyz_host = out_xyz_host;
+  msm_run_entry(ctx, &e, job);
 }
 
 const MsmSmallVtbl* msm_small_vtbl_c01();

@@ -42,7 +42,7 @@ struct MsmVtbl {
   // dst < 0x80000000: bucket index (single-task bucket), else partial slot (dst & 0x7fffffff)
   // desc[t] = {first entry, length, dst, -} of the t-th task IN SCHEDULE ORDER (task_order_kernel): one coalesced 16-B load per
   // lane instead of four dependent random ones
-  // init != 0: the bucket array already holds the buckets of another MSM (bucket chaining, ctx.hpp): a single-task bucket starts
+  // init != 0: the bucket array already holds the buckets of another MSM (bucket chaining, internal.hpp MsmJob): a single-task bucket starts
   // from its stored value instead of the identity
   // tune: the launcher's choices (LDS bytes, waves per SIMD the kernel was compiled for): it has no context of its own
   void (*accumulate)(hipStream_t, const zkp_tune& tune, const char* table, const uint32_t* vals, const uint4* desc,

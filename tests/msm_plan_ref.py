@@ -3,6 +3,8 @@ csrc/msm_digits.hpp.
 
 Nothing here is taken from the device or from the library: tests/test_msm_plan_ref.py checks the model's own invariants on the
 CPU, tests/test_gpu_msm_plans.py compares the plan the library prints at upload with this one and builds its edge scalars from it.
+sort_plan / sched_layout model the geometry of the bucket sort and of the task schedule; tests/test_msm_sort_plan.py compares
+csrc/msm_sort_plan.hpp with them.
 
 One place where the model is exact and the library is not: round(log2 n) turns at sqrt(2) 2^k, which the library writes as the
 decimal 1.41421356.  The two disagree only for an integer n in [1.41421356 2^k, sqrt(2) 2^k); the smallest such n is 189812531
@@ -136,6 +138,64 @@ def chunk_lengths(n: int, chunk_points: int, chunk_first: int = 2):
     while rest > 0:
         out.append(min(per_rest, rest))
         rest -= out[-1]
+    return out
+
+
+# The bucket sort and the task schedule (csrc/msm.hip K6 / K7), as the host code sized them before csrc/msm_sort_plan.hpp existed
+SORT_H1_MAX, SORT_L_MAX = 13, 13         # level-1 bins <= 8192 (static LDS histogram), level-2 keys per bin <= 8192
+SORT_BIN_TARGET = 16384                  # entries per level-1 bin the level-2 kernel stages in LDS
+SORT_SCALARS = 2048                      # scalars per level-1 tile, more for large MSMs
+SORT_STAGE_BYTES = 56 * 1024             # LDS stage of the staged level-1 scatter
+SORT_BIN_STAGE = 20480                   # values the level-2 kernel stages in LDS
+TM_WORDS = 512                           # the schedule's tmeta block
+U32 = 0xFFFFFFFF
+
+
+def sort_plan(n: int, W: int, sets: int, kbits: int, forced_h1: int = 0, staged_enabled: bool = True):
+    """-> None when the shape is refused, else a dict.  E = n W sets entries go into 2^H1 level-1 bins: 10 bits, more (up to 13)
+    while a bin would hold more than SORT_BIN_TARGET entries; a forced value (> 0, at most 13) replaces that; never more than
+    the kbits of a bucket id, and at least kbits - 13 so that a bin has at most 2^13 keys.  Refused when H1 < log2(sets): a bin
+    would straddle two scalar vectors.  Tiles of 2048 scalars, grown by 256 until there are at most 1536 of them.  The staged
+    scatter runs with at most 2048 bins per vector when 256 scalars' entries (8 bytes each) fit the stage, in sub-rounds of as
+    many scalars as fit, a multiple of 256, at most a tile."""
+    lgs = (sets - 1).bit_length()
+    E = n * W * sets
+    H1 = 10
+    while H1 < SORT_H1_MAX and (E >> H1) > SORT_BIN_TARGET:
+        H1 += 1
+    if forced_h1 > 0:
+        H1 = min(SORT_H1_MAX, forced_h1)
+    H1 = min(H1, kbits)
+    if kbits - H1 > SORT_L_MAX:
+        H1 = kbits - SORT_L_MAX
+    if H1 < lgs:
+        return None
+    LB = kbits - H1
+    nbins1 = 1 << H1
+    nbins_set = nbins1 >> lgs
+    tile = SORT_SCALARS
+    while -(-n // tile) > 1536:
+        tile += 256
+    nblocks = -(-n // tile)
+    staged_sub = staged_lds = 0
+    if staged_enabled and nbins_set <= 2048 and 256 * W * 8 <= SORT_STAGE_BYTES:
+        staged_sub = min(SORT_STAGE_BYTES // (W * 8) // 256 * 256, tile)
+        staged_lds = (nbins_set + ((nbins_set + 3) & ~3)) * 4 + staged_sub * W * 8
+    return dict(H1=H1, LB=LB, nbins1=nbins1, nbins_set=nbins_set, tile=tile, nblocks=nblocks, hist_n=nbins1 * nblocks + 1,
+                staged_sub=staged_sub, staged_lds=staged_lds, bin_lds=(4 << LB) + 4 * SORT_BIN_STAGE)
+
+
+def sched_layout(nb: int, E: int, cap: int):
+    """The schedule's arrays in one buffer of 32-bit words: tcount and toff (nb + 2 words each), task_start, task_len, task_dst and
+    long_list (max_tasks each), tmeta (TM_WORDS), then, at the next 16-byte boundary, max_tasks 16-byte descriptors; 8 words spare.
+    max_tasks = nb + E / cap + 1 in 32-bit arithmetic."""
+    max_tasks = (nb + ((E // cap) & U32) + 1) & U32
+    out = dict(max_tasks=max_tasks, words=2 * (nb + 2) + 8 * max_tasks + TM_WORDS + 8, tcount=0, toff=nb + 2)
+    at = 2 * (nb + 2)
+    for name in ("task_start", "task_len", "task_dst", "long_list", "tmeta"):
+        out[name] = at
+        at += max_tasks
+    out["desc_bytes"] = ((out["tmeta"] + TM_WORDS) * 4 + 15) & ~15
     return out
 
 

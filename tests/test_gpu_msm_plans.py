@@ -1,7 +1,7 @@
 """Every MSM window plan, sort path and reduction variant, in-process and at small sizes.
 
-msm_run_entry (csrc/msm.hip) picks between many kernel paths by the public window bits / chunk size / table budget of
-zkp_ctx_config and by the internal switches of csrc/tune.hpp.  Each case below is ONE context created under one such setting
+msm_run_entry (csrc/msm.hip: the phases of MsmRun, sized by csrc/msm_sort_plan.hpp) picks between many kernel paths by the
+public window bits / chunk size / table budget of zkp_ctx_config and by the internal switches of csrc/tune.hpp.  Each case below is ONE context created under one such setting
 (latched at creation; the environment is clean again before anything is uploaded), and every (curve, group) runs inside it:
 
   * the plan the library prints at upload (ZKP_DEBUG_MSM, read live by bases_upload; the context itself latched it as 0) must equal
@@ -23,7 +23,7 @@ import re
 import numpy as np
 import pytest
 
-from ckb_zkp_amd import codec
+from ckb_zkp_amd import _lib, codec
 from ckb_zkp_amd.params import get_curve
 from oracle.pyref.curves import Group
 from tests import msm_plan_ref as M
@@ -436,3 +436,33 @@ def test_chunked_msm_at_the_smallest_chunk(variant_ctx, inputs, capfd, monkeypat
                     v.dev_free(kd)
                 assert affine(I, outs[0]) == I.multi_exp(N_MULTI, 0)
                 assert affine(I, outs[1]) == I.point(sum(a * b for a, b in zip(I.multi_d[10:], I.multi_k[10:])))
+
+
+# ------------------------------------------------------------------------------------------- K: nothing is left for the next MSM
+def test_no_chain_request_outlives_its_msm(ctx, inputs):
+    """One context, in this order: a stand-alone MSM; a Groth16 proof at 2^6 whose L query defers its reduction to H (the bucket
+    chain travels in each MSM's own request); the stand-alone MSM refused for a freed bases handle; the stand-alone MSM again,
+    with the first call's result."""
+    from tests.test_gpu_groth16_fused import _setup
+    I = inputs("bn254", 1)
+    b = ctx.upload_bases(I.c, 1, I.multi_xy, I.multi_inf)
+    gone = ctx.upload_bases(I.c, 1, I.multi_xy[:N_EDGE], I.multi_inf[:N_EDGE])
+    pk, c, zs = _setup(ctx, "bn254", 6)
+    try:
+        first = b.msm(I.multi)
+        assert affine(I, first) == I.multi_exp(N_MULTI, 0)
+        assert pk.table_plan()["l_h_bucket_chained"]
+        one = codec.fr_to_mont([1], c).reshape(-1, 4)
+        out, _ = pk.prove_raw(zs[0], one[0], one[0], z_on_device=False)
+        assert out.any()
+        stale = gone.handle
+        gone.free()
+        gone.handle = stale
+        with pytest.raises(_lib.ZkpError) as err:
+            gone.msm(I.multi[:N_EDGE])
+        assert err.value.status == -6                                          # include/zkp_accel.h ZKP_ERR_BAD_HANDLE
+        assert affine(I, b.msm(I.multi)) == affine(I, first)                   # (the Jacobian limbs depend on the order inside a bucket)
+    finally:
+        gone.handle = 0
+        pk.free()
+        b.free()
