@@ -175,6 +175,11 @@ SIGNATURES = {
     "zkp_fr_ipa_fold_ab_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp, vp]),
     "zkp_fr_asvc_subset_weights_dev": (C.c_int32, [vp, C.c_int, C.c_uint32, vp, C.c_size_t, vp, vp]),
     "zkp_fr_asvc_quotient_dev": (C.c_int32, [vp, C.c_int, vp, C.c_uint32, vp, C.c_size_t, vp]),
+    "zkp_pedersen_key_create": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp, C.POINTER(vp)]),
+    "zkp_pedersen_key_free": (C.c_int32, [vp, vp]),
+    "zkp_pedersen_key_info": (C.c_int32, [vp, u64p]),
+    "zkp_pedersen_commit_rows_dev": (C.c_int32, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]),
+    "zkp_fr_vecmat_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

@@ -415,6 +415,63 @@ class Context:
                                                      C.c_void_p(q_ptr or 0)), "zkp_fr_asvc_quotient_dev")
         self.sync()                                               # `pos` is host memory of this call
 
+    def pedersen_key_create(self, curve, gens_xy, gens_inf, h_xy) -> int:
+        """zkp_pedersen_key_create: the resident window tables of the (n, w) affine Montgomery generators (flags None = none) and
+        the blinding generator h -> key handle (free it with pedersen_key_free)."""
+        xy, h = _c64(gens_xy), _c64(h_xy)
+        n = xy.shape[0] if xy.ndim == 2 else 0
+        infa = None if gens_inf is None else np.ascontiguousarray(gens_inf, dtype=np.uint8)
+        assert infa is None or infa.shape[0] >= n
+        key = C.c_void_p()
+        _lib.check(self.lib.zkp_pedersen_key_create(self.h, get_curve(curve).cid, _ptr(xy), _ptr(infa), n, _ptr(h), C.byref(key)),
+                   "zkp_pedersen_key_create")
+        return key.value
+
+    def pedersen_key_free(self, key: int):
+        _lib.check(self.lib.zkp_pedersen_key_free(self.h, C.c_void_p(key or 0)), "zkp_pedersen_key_free")
+
+    def pedersen_key_info(self, key: int) -> dict:
+        """zkp_pedersen_key_info -> n_gens, c, W, pairs_per_slice, gens_per_slice (G), table_bytes, lds_bytes, launches"""
+        info = (C.c_uint64 * 8)()
+        _lib.check(self.lib.zkp_pedersen_key_info(C.c_void_p(key or 0), info), "zkp_pedersen_key_info")
+        return {"n_gens": info[0], "c": info[1], "W": info[2], "pairs_per_slice": info[3], "gens_per_slice": info[3] // info[2],
+                "table_bytes": info[4], "lds_bytes": info[5], "launches": info[6]}
+
+    def pedersen_commit_rows_dev(self, key: int, scalars_ptr: int, rows: int, cols: int, blinds_ptr, out_xy_ptr: int, out_inf_ptr: int):
+        """zkp_pedersen_commit_rows_dev: out[i] = sum_j scalars[i cols + j] g_j + blinds[i] h over DEVICE Montgomery Fr (blinds None /
+        0: no blind term) -> rows affine Montgomery points and flags in DEVICE memory.  Launches only."""
+        _lib.check(self.lib.zkp_pedersen_commit_rows_dev(self.h, C.c_void_p(key or 0), C.c_void_p(scalars_ptr or 0), rows, cols,
+                                                         C.c_void_p(blinds_ptr or 0), C.c_void_p(out_xy_ptr or 0),
+                                                         C.c_void_p(out_inf_ptr or 0)), "zkp_pedersen_commit_rows_dev")
+
+    def pedersen_commit_rows(self, curve, key: int, scalars_mont, blinds_mont=None):
+        """Host convenience over pedersen_commit_rows_dev: (rows, cols, 4) Montgomery scalars and (rows, 4) blinds or None ->
+        ((rows, w) affine Montgomery, (rows,) identity flags)."""
+        s = _c64(scalars_mont)
+        rows, cols = s.shape[0], s.shape[1]
+        out = np.zeros((rows, 2 * get_curve(curve).fq_limbs), dtype=np.uint64)
+        inf = np.zeros(rows, dtype=np.uint8)
+        bufs = []
+        try:
+            def up(a):
+                d = self.to_device(a)
+                bufs.append(d)
+                return d
+            ds, do, di = up(s), up(out), up(inf)
+            db = None if blinds_mont is None else up(_c64(blinds_mont))
+            self.pedersen_commit_rows_dev(key, ds, rows, cols, db, do, di)
+            self.d2h(out, do)
+            self.d2h(inf, di)
+            return out, inf
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+
+    def fr_vecmat_dev(self, curve, l_ptr: int, m_ptr: int, rows: int, cols: int, out_ptr: int):
+        """zkp_fr_vecmat_dev: out[j] = sum_i l[i] m[i cols + j] over DEVICE Montgomery Fr.  Launches only."""
+        _lib.check(self.lib.zkp_fr_vecmat_dev(self.h, get_curve(curve).cid, C.c_void_p(l_ptr or 0), C.c_void_p(m_ptr or 0), rows, cols,
+                                              C.c_void_p(out_ptr or 0)), "zkp_fr_vecmat_dev")
+
     def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
         """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
         Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""

@@ -61,6 +61,7 @@ for _c, _g in CONFIGS:
     UNITS.append(("msm_small.hip", f"msm_small_c{_c}{_g}.o", _d + UNROLL))   # batched small variable-base MSM (own launch table)
 for _c in (0, 1):
     UNITS.append(("ipa.hip", f"ipa_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"] + UNROLL))       # IPA generator fold, G1 (own launch table)
+    UNITS.append(("pedersen.hip", f"pedersen_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"] + UNROLL))   # resident Pedersen key, row commitments + Fr vector-matrix product, G1 (own launch table)
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result",
          "-ffp-contract=off"]
 

@@ -13,6 +13,7 @@
 #include "internal.hpp"
 #include "ipa.hpp"
 #include "fr_open.hpp"
+#include "pedersen.hpp"
 #include "plonk.hpp"
 #include "spark.hpp"
 #include "stream_place.hpp"
@@ -895,6 +896,32 @@ int32_t zkp_fr_asvc_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t
                                  const uint32_t* positions_host, size_t k, uint64_t* q_dev) {
   if (!phi_dev || !positions_host || !q_dev) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { asvc_quotient(ctx, curve, phi_dev, log_n, positions_host, k, q_dev); });
+}
+int32_t zkp_pedersen_key_create(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* gens_xy_host, const uint8_t* gens_inf_host,
+                                size_t n_gens, const uint64_t* h_xy_host, zkp_pedersen_key** out) {
+  if (!gens_xy_host || !h_xy_host || !out) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pedersen_vtbl(curve)->key_create(ctx, gens_xy_host, gens_inf_host, n_gens, h_xy_host, out); });
+}
+int32_t zkp_pedersen_key_free(zkp_ctx* ctx, zkp_pedersen_key* key) {
+  if (!key) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pedersen_key_free(ctx, key); });
+}
+int32_t zkp_pedersen_key_info(const zkp_pedersen_key* key, uint64_t* info) {
+  if (!key || !info) return ZKP_ERR_BAD_ARG;
+  pedersen_key_info(key, info);
+  return ZKP_OK;
+}
+int32_t zkp_pedersen_commit_rows_dev(zkp_ctx* ctx, const zkp_pedersen_key* key, const uint64_t* scalars_dev, size_t rows, size_t cols,
+                                     const uint64_t* blinds_dev, uint64_t* out_xy_dev, uint8_t* out_inf_dev) {
+  if (!key || !scalars_dev || !out_xy_dev || !out_inf_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    pedersen_vtbl(pedersen_key_curve(key))->commit_rows(ctx, key, scalars_dev, rows, cols, blinds_dev, out_xy_dev, out_inf_dev);
+  });
+}
+int32_t zkp_fr_vecmat_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_dev, const uint64_t* m_dev, size_t rows, size_t cols,
+                          uint64_t* out_dev) {
+  if (!l_dev || !m_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pedersen_vtbl(curve)->vecmat(ctx, l_dev, m_dev, rows, cols, out_dev); });
 }
 int32_t zkp_bench_mulmod(zkp_ctx* ctx, zkp_curve_t curve, int32_t field, int32_t unsaturated, double* out) {
   if (!out || (curve != ZKP_BN254 && curve != ZKP_BLS12_381) || field < 0 || field > 1) return ZKP_ERR_BAD_ARG;

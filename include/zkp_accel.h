@@ -56,7 +56,9 @@ const char* zkp_status_string(int32_t status);
  * then zkp_fr_poly_eval_many_dev / zkp_fr_lincomb_dev (PLONK evaluations and opening polynomials),
  * then zkp_fr_gkr_eval_layer_batch_dev / zkp_fr_gkr_dp_round_dev (Hyrax data-parallel GKR),
  * then zkp_fr_powers_dev / zkp_fr_bp_t_coeffs_dev / zkp_fr_bp_lr_eval_dev / zkp_fr_ipa_fold_ab_dev (Bulletproofs R1CS prover),
- * then zkp_fr_asvc_subset_weights_dev / zkp_fr_asvc_quotient_dev (aSVC subvector commitments).
+ * then zkp_fr_asvc_subset_weights_dev / zkp_fr_asvc_quotient_dev (aSVC subvector commitments),
+ * then zkp_pedersen_key_create / zkp_pedersen_key_free / zkp_pedersen_key_info / zkp_pedersen_commit_rows_dev / zkp_fr_vecmat_dev
+ * (matrix polynomial commitments over a resident Pedersen key).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -472,6 +474,57 @@ int32_t zkp_fr_asvc_subset_weights_dev(zkp_ctx* ctx, zkp_curve_t curve, uint32_t
  * zkp_fr_vec_op_dev.  ZKP_ERR_BAD_ARG: the rules above, a NULL or misaligned phi_dev / q_dev, q_dev overlapping phi_dev. */
 int32_t zkp_fr_asvc_quotient_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* phi_dev, uint32_t log_n,
                                  const uint32_t* positions_host, size_t k, uint64_t* q_dev);
+/* Matrix polynomial commitments over a resident Pedersen key (later in 0.7.1, detected by symbol): `packing_poly_commit` /
+ * `poly_commit_vec` of hyrax, libra and spartan (spartan/src/commitments.rs:10-56, libra/src/evaluate.rs:130-170) and the row fold
+ * of LogDotProductProof::reduce_prover (hyrax/src/commitment.rs:335-578).  BN254 / BLS12-381 G1.  The logarithmic argument after
+ * the fold is zkp_g1_ipa_fold_dev + zkp_msm_g1_var_batch_dev; the transcript, the blinds and the challenges stay with the caller.
+ *
+ * The key: n_gens generators (`gen_n` of PolyCommitmentSetupParameters) and the blinding generator h, affine Montgomery points in
+ * HOST memory in the layout of zkp_bases_upload_g1; gens_inf_host: identity flags or NULL (= none); a (0, 0) point is an identity
+ * too, and an identity stays one at every level.  1 <= n_gens <= ZKP_PEDERSEN_MAX_GENS (== ZKP_MSM_SMALL_MAX_G1, so every round of
+ * the inner-product argument that follows stays inside the batch MSM's cap).  The key holds the window tables 2^(c w) g_j, w < W =
+ * floor((256 + c) / c), as affine points in device memory (h is generator n_gens): W (n_gens + 1) points of 64 / 96 bytes, c = 8.
+ * Creation is one-time work, exact, 2 W launches (c doublings per level in registers, one batch inversion per 64 points and level);
+ * it runs on the context's current stream, takes scratch from the context's grow-only arena and returns when the tables are
+ * built.  ZKP_ERR_BAD_ARG: a NULL gens_xy_host / h_xy_host / out, n_gens outside the rule; ZKP_ERR_OOM: the tables do not fit;
+ * on an error *out is untouched.  A key belongs to the context that created it; zkp_pedersen_key_free waits for that context's
+ * current stream first.
+ * zkp_pedersen_key_info: info[0] n_gens, [1] c, [2] W, [3] (generator, window) pairs per slice at most (G W with G = floor(4096 / W)
+ * generators), [4] table bytes, [5] LDS bytes of one workgroup of the bucket pass, [6] launches per commitment call, [7] 0. */
+#define ZKP_PEDERSEN_MAX_GENS 65536
+typedef struct zkp_pedersen_key zkp_pedersen_key;
+int32_t zkp_pedersen_key_create(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* gens_xy_host, const uint8_t* gens_inf_host,
+                                size_t n_gens, const uint64_t* h_xy_host, zkp_pedersen_key** out);
+int32_t zkp_pedersen_key_free(zkp_ctx* ctx, zkp_pedersen_key* key);
+int32_t zkp_pedersen_key_info(const zkp_pedersen_key* key, uint64_t* info);
+/* out[i] = (sum_{j < cols} scalars[i cols + j] g_j + blinds[i] h).into_affine() for i < rows; blinds_dev == NULL: no blind term.
+ * rows == 1 is poly_commit_vec.  scalars_dev: rows x cols Fr, row-major; blinds_dev: rows Fr; both Montgomery (into_repr() fused),
+ * 16-byte aligned, device memory.  out_xy_dev: rows affine Montgomery points (16-byte aligned), out_inf_dev: rows flags, device
+ * memory; every point is the canonical affine form (bit-exact results) and an identity is written exactly as
+ * zkp_fixed_base_mul_g1 writes it (words and flag).  rows >= 1, 1 <= cols <= n_gens, rows * cols <= 2^28.
+ * Three launches whatever rows and cols are, no host loop over rows: one wave per (row, slice of <= G generators) walks every
+ * scalar's W signed window digits once, sorts the <= 4096 (generator, window) pairs by bucket (stable counting sort in LDS) and
+ * accumulates them into 2^(c-1) LDS buckets conflict-free and in a fixed order, then reduces sum_b (b + 1) B_b — the tables carry
+ * the window weights, so there is no doubling tail; one wave per row adds the slices and the blind term; one lane per row
+ * converts to affine with one inversion per 64 rows.  All additions are complete (equal, opposite and identity operands).
+ * ZKP_ERR_BAD_ARG: a NULL key / scalars_dev / out_xy_dev / out_inf_dev, a key of another context, a misaligned scalars_dev /
+ * blinds_dev / out_xy_dev, rows or cols outside the rules, an output overlapping an input or the other output.  Scratch:
+ * rows * (ceil(cols / G) + 1) bucket points (144 / 224 bytes) from the context's grow-only arena (ZKP_ERR_OOM if it cannot grow).
+ * Every argument is checked before anything runs: on an error the outputs are untouched.  Runs on the context's current stream;
+ * launches only, like zkp_fr_vec_op_dev. */
+int32_t zkp_pedersen_commit_rows_dev(zkp_ctx* ctx, const zkp_pedersen_key* key, const uint64_t* scalars_dev, size_t rows, size_t cols,
+                                     const uint64_t* blinds_dev, uint64_t* out_xy_dev, uint8_t* out_inf_dev);
+/* out[j] = sum_{i < rows} l[i] m[i cols + j] for j < cols: the row fold lz = L^T M of reduce_prover.  l_dev: rows Fr, m_dev:
+ * rows x cols Fr row-major, out_dev: cols Fr; Montgomery, canonical, 16-byte aligned, device memory; every element written is the
+ * canonical Montgomery representative.  rows >= 1, cols >= 1, rows * cols <= 2^28; out_dev overlaps neither input.
+ * Lanes take consecutive columns (coalesced loads), a workgroup ZKP_FR_VECMAT_ROW_CHUNK rows; with more than one chunk the partial
+ * sums go to the context's grow-only arena (32 * cols * ceil(rows / ZKP_FR_VECMAT_ROW_CHUNK) bytes) and a second launch adds them
+ * in chunk order: two launches at most.  ZKP_ERR_BAD_ARG: a NULL or misaligned pointer, a shape outside the rules, out_dev
+ * overlapping l_dev or m_dev.  Every argument is checked before anything runs: on an error out_dev is untouched.  Runs on the
+ * context's current stream; launches only. */
+#define ZKP_FR_VECMAT_ROW_CHUNK 32
+int32_t zkp_fr_vecmat_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_dev, const uint64_t* m_dev, size_t rows, size_t cols,
+                          uint64_t* out_dev);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
