@@ -164,6 +164,13 @@ __global__ void scalar_tail_kernel(uint32_t* tail, const uint32_t* rs, size_t ta
   (r * s).neg().store(tail + 24);
 }
 
+// The one curve dispatch: f(P{}) with P the Fr parameter struct of `curve`; f is a generic lambda that names it as decltype(P)
+template <class F>
+static auto with_fr(int curve, F&& f) {
+  if (curve == ZKP_BN254) return f(Bn254Fr{});
+  return f(Bls381Fr{});
+}
+
 static DevCsr upload_csr(zkp_ctx* ctx, const zkp_csr& m, uint32_t rows) {
   DevCsr d;
   ZKP_REQUIRE(m.row_ptr != nullptr, ZKP_ERR_BAD_ARG);
@@ -284,13 +291,10 @@ static void lagrange_h(zkp_ctx* ctx, int curve, const uint64_t* h_query, const u
   uint32_t* dtw = d_tw.as<uint32_t>(ntw * 8);
   uint32_t* dconst = dscal + N * 8;
   ZKP_HIP(hipMemcpyAsync(dconst, hconst, sizeof hconst, hipMemcpyHostToDevice, st));
-  if (curve == ZKP_BN254) {
-    hipLaunchKernelGGL(pow_canon_kernel<Bn254Fr>, dim3((N + 255) / 256), dim3(256), 0, st, dscal, dconst, dconst + 8, (uint32_t)N);
-    hipLaunchKernelGGL(pow_canon_kernel<Bn254Fr>, dim3((ntw + 255) / 256), dim3(256), 0, st, dtw, dconst + 16, dconst + 24, (uint32_t)ntw);
-  } else {
-    hipLaunchKernelGGL(pow_canon_kernel<Bls381Fr>, dim3((N + 255) / 256), dim3(256), 0, st, dscal, dconst, dconst + 8, (uint32_t)N);
-    hipLaunchKernelGGL(pow_canon_kernel<Bls381Fr>, dim3((ntw + 255) / 256), dim3(256), 0, st, dtw, dconst + 16, dconst + 24, (uint32_t)ntw);
-  }
+  with_fr(curve, [&](auto P) {
+    hipLaunchKernelGGL(pow_canon_kernel<decltype(P)>, dim3((N + 255) / 256), dim3(256), 0, st, dscal, dconst, dconst + 8, (uint32_t)N);
+    hipLaunchKernelGGL(pow_canon_kernel<decltype(P)>, dim3((ntw + 255) / 256), dim3(256), 0, st, dtw, dconst + 16, dconst + 24, (uint32_t)ntw);
+  });
   char* X = d_X.as<char>(N * v1->bucket_bytes);           // stage points in the bucket (unsaturated) layout
   char* oxy = d_oxy.as<char>(N * ab);
   uint8_t* oinf = d_oinf.as<uint8_t>(N);
@@ -659,8 +663,7 @@ zkp_groth16_pk* groth16_pk_upload(zkp_ctx* ctx, const zkp_groth16_pk_desc* d, in
     }
   }
   uint32_t* consts = pk->consts.as<uint32_t>(64);
-  if (d->curve == ZKP_BN254) hipLaunchKernelGGL(qap_consts_kernel<Bn254Fr>, dim3(1), dim3(64), 0, ctx->cur->stream, consts, lg);
-  else hipLaunchKernelGGL(qap_consts_kernel<Bls381Fr>, dim3(1), dim3(64), 0, ctx->cur->stream, consts, lg);
+  with_fr(d->curve, [&](auto P) { hipLaunchKernelGGL(qap_consts_kernel<decltype(P)>, dim3(1), dim3(64), 0, ctx->cur->stream, consts, lg); });
   ZKP_HIP(hipGetLastError());
   for (int l = 0; l < 2; l++) {                     // further lanes allocate on first use
     auto& L = pk->lane[l];
@@ -715,7 +718,7 @@ void groth16_pk_info(zkp_ctx* ctx, zkp_groth16_pk* pk, uint64_t info[8]) {
 // key: the pointwise values v on the coset, the scalars of its H MSM
 template <class P>
 static uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, bool coeffs = true, int g = 0, int G = 1) {
-  // g, G: proof g of a fused group of G (prove_enqueue_part) works in the g-th of G abc regions of the lane
+  // g, G: proof g of a fused group of G (ProofJob) works in the g-th of G abc regions of the lane
   const uint32_t N = (uint32_t)pk->N;
   uint32_t* a = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8 * (size_t)G) + (size_t)g * 3 * pk->N * 8;
   uint32_t* b = a + pk->N * 8;
@@ -766,267 +769,392 @@ void groth16_witness_map(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, ui
     ZKP_HIP(hipMemcpyAsync(s, z, pk->nz * 32, hipMemcpyHostToDevice, ctx->cur->stream));
     zd = s;
   }
-  uint32_t* hd = pk->curve == ZKP_BN254 ? witness_map_dev<Bn254Fr>(ctx, pk, zd) : witness_map_dev<Bls381Fr>(ctx, pk, zd);
+  uint32_t* hd = with_fr(pk->curve, [&](auto P) { return witness_map_dev<decltype(P)>(ctx, pk, zd); });
   ZKP_HIP(hipMemcpyAsync(h, hd, pk->N * 32, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->cur->stream));
   if (!on_device) ZKP_HIP(hipStreamSynchronize(ctx->cur->stream));
 }
 
-// Enqueue one proof on the current lane (ctx->cur): everything is asynchronous up to and including the read-back of
-// the 3 proof points into the lane's pinned host buffer; prove_finish() synchronises the lane and hands them out.
-// part: 1 = copy the inputs (z, r, s) into the lane's buffers, 2 = everything else (the part a hipGraph captures), 3 = both
-// G > 1: a FUSED GROUP of G proofs over the same key in the kernel chain of one (zg[g], r + 4 g, s + 4 g; z is unused).  The
-// inputs lie in group-wide buffers (S: G vectors of nz + 4 scalars; [r, s] pairs 16 words apart), one scalar_tail launch covers
+// ---- the buffers of the prove path: each layout is built in one place, by the code that writes it and by the code that reads it ----
+constexpr size_t MAX_FN1 = 12, MAX_FN2 = 24;   // 32-bit words of a G1 / G2 coordinate on the largest curve (BLS12-381; MsmVtbl::fN)
+constexpr size_t RS_STEP = 16;                 // words between the [r, s] pairs of two proofs (scalar_tail_kernel, assemble_g1_part1)
+constexpr size_t FLAG_STEP = 4;                // words between the identity flags of two proofs (three are used)
+
+// 32-bit words of the three proof points (A and C in G1, B in G2).  The proof as it is handed out: A = 2 fN1 | B = 2 fN2 | C = 2 fN1
+struct ProofWords {
+  size_t fN1, fN2;
+  explicit ProofWords(int curve) : fN1((size_t)msm_vtbl(curve, 1)->fN), fN2((size_t)msm_vtbl(curve, 2)->fN) {
+    ZKP_REQUIRE(fN1 <= MAX_FN1 && fN2 <= MAX_FN2, ZKP_ERR_UNSUPPORTED_CURVE);
+  }
+  size_t affine() const { return 4 * fN1 + 2 * fN2; }
+  int b_off() const { return (int)(2 * fN1); }
+  int c_off() const { return (int)(2 * fN1 + 2 * fN2); }
+};
+constexpr size_t MAX_PROOF_WORDS = 4 * MAX_FN1 + 2 * MAX_FN2;
+static_assert(MAX_PROOF_WORDS <= ASM_OUT_STEP, "an affine proof fits its slot of a fused group's device proofs");
+
+// The lane's device proof buffer (PerLane::proof) for a group of G proofs: G x [r, s] | G x ASM_OUT_STEP proof words | G x flags
+struct LaneProofBuf {
+  static constexpr size_t WORDS = 1024;        // reserved per proof
+  uint32_t *rs, *proof, *flags;
+  LaneProofBuf(DevBuf& b, int G) : rs(b.as<uint32_t>(WORDS * G)), proof(rs + RS_STEP * G), flags(proof + ASM_OUT_STEP * G) {}
+};
+static_assert(RS_STEP + ASM_OUT_STEP + FLAG_STEP <= LaneProofBuf::WORDS, "[r, s], proof and flags fit what a proof reserves");
+
+// The pinned landing zone of proof g of the lane's group (zkp_lane::host_proof holds MAX_FUSE of them).  Device tail: the affine
+// proof at 0, its three flags at FLAGS.  Host tail: the points A | B | C as XYZZ, which prove_finish makes affine.
+struct HostProofZone {
+  static constexpr size_t FLAGS = 256;
+  uint32_t *base, *a, *b, *c, *flags;
+  HostProofZone(const zkp_lane* lane, int g, const ProofWords& w)
+      : base(lane->host_proof + (size_t)g * zkp_lane::HOST_PROOF_WORDS), a(base), b(a + 4 * w.fN1), c(b + 4 * w.fN2), flags(base + FLAGS) {}
+};
+static_assert(MAX_PROOF_WORDS <= HostProofZone::FLAGS, "the affine proof ends in front of its flags");
+static_assert(HostProofZone::FLAGS + 3 <= zkp_lane::HOST_PROOF_WORDS, "the flags lie inside the landing zone");
+static_assert(8 * MAX_FN1 + 4 * MAX_FN2 <= zkp_lane::HOST_PROOF_WORDS, "three XYZZ points fit the landing zone");
+
+// ctx->msm_misc as the two assembly entry points carve it: in_words of input | [r, s] | 6 result slots | the proof | its flags
+struct AssembleBuf {
+  static constexpr size_t PROOF_WORDS = 240, TAIL_WORDS = 256 + 16;      // the proof; proof + flags as reserved
+  uint32_t *in, *rs;
+  char* res;
+  uint32_t *proof, *flags;
+  AssembleBuf(zkp_ctx* ctx, size_t slot, size_t in_words) {
+    in = ctx->msm_misc.as<uint32_t>(in_words + RS_STEP + 6 * slot / 4 + TAIL_WORDS);
+    rs = in + in_words;
+    res = reinterpret_cast<char*>(rs + RS_STEP);
+    proof = reinterpret_cast<uint32_t*>(res + 6 * slot);
+    flags = proof + PROOF_WORDS;
+  }
+  void upload_rs(hipStream_t st, const uint64_t* r, const uint64_t* s) const {
+    ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
+    ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
+  }
+};
+static_assert(MAX_PROOF_WORDS <= AssembleBuf::PROOF_WORDS && AssembleBuf::PROOF_WORDS + FLAG_STEP <= AssembleBuf::TAIL_WORDS,
+              "proof and flags fit the tail of the carve-up");
+
+// One proof, or one fused group of proofs, to enqueue on the current lane (ctx->cur); filled by field assignment.
+// G > 1: a FUSED GROUP of G proofs over the same key in the kernel chain of one.  The
+// inputs lie in group-wide buffers (S: G vectors of nz + 4 scalars; [r, s] pairs RS_STEP words apart), one scalar_tail launch covers
 // the group, every MSM runs as ONE MSM over G scalar vectors (msm.hip `sets`: window tables, sort passes, task schedule, accumulate
 // and reduction launches shared), the results fill G x 6 slots and every assembly kernel runs one workgroup per proof.  The
 // witness map runs once per proof: the group's a and b vectors through one batched transform per kind (ntt_run_batch) measured
 // the same (profiles/proof_fusion_bench.txt).  Only with the default stream plan of a pipelined batch.
-template <class FrP>
-static void prove_enqueue_part(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
-                               const uint64_t* s, int part, char* partial_out = nullptr, bool latency_plan = false, int G = 1,
-                               const uint64_t* const* zg = nullptr) {
-  // partial_out != nullptr (base-sharded key): no assembly; the 5 XYZZ sums of this rank's slices (A | B1 | B2 | H | L,
-  // G2-sized slots) are left at partial_out (device) for the all-gather
-  ZKP_REQUIRE((pk->shard_world > 0) == (partial_out != nullptr), ZKP_ERR_BAD_ARG);
-  ZKP_REQUIRE(pk->hA != 0, ZKP_ERR_BAD_ARG);             // matrices-only key: use the sharded path
-  zkp_groth16_pk::PerLane& PL = pk->lane[ctx->cur_idx];
-  hipStream_t st = ctx->cur->stream;
-  const bool prof = ctx->profiling;
-  // zkp_ctx_config.host_affine = ZKP_OFF / ZKP_HOST_AFFINE=0: into_affine of the proof points on the device (rounds 1-3) instead of the host
-  const bool host_tail = ctx->cfg.host_affine && !partial_out;
-  zkp_groth16_timing tm{};
-  struct ProfEvents {                                   // destroyed on every exit path (msm_run may throw)
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~ProfEvents() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } pev;
-  if (prof)
-    for (hipEvent_t& x : pev.e) ZKP_HIP(hipEventCreate(&x));
-  hipEvent_t &e0 = pev.e[0], &e1 = pev.e[1], &eT0 = pev.e[2], &eT1 = pev.e[3];
-  auto tic = [&] { if (prof) ZKP_HIP(hipEventRecord(e0, st)); };
-  auto toc = [&](float* dst) {
-    if (!prof) return;
-    ZKP_HIP(hipEventRecord(e1, st));
-    ZKP_HIP(hipEventSynchronize(e1));
-    ZKP_HIP(hipEventElapsedTime(dst, e0, e1));
-  };
-  if (prof) ZKP_HIP(hipEventRecord(eT0, st));
-  ZKP_REQUIRE(G >= 1 && G <= zkp_lane::MAX_FUSE && (G == 1 || (zg && part == 3 && !partial_out && !prof)), ZKP_ERR_BAD_ARG);
-  const size_t s_stride = pk->nz + 4;                 // scalars between the S vectors of two proofs of a group
-  uint32_t* S = PL.S.as<uint32_t>(s_stride * 8 * G);
-  uint32_t* rs = PL.proof.as<uint32_t>((size_t)1024 * G);   // G x [r, s], then G x ASM_OUT_STEP proof words, then G x 4 flags
-  uint32_t* proof_dev = rs + 16 * G;
-  uint32_t* flags_dev = proof_dev + ASM_OUT_STEP * G;
-  if (part & 1) {
-    for (int g = 0; g < G; g++) {
-      ZKP_HIP(hipMemcpyAsync(S + g * s_stride * 8, G > 1 ? zg[g] : z, pk->nz * 32, z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-      ZKP_HIP(hipMemcpyAsync(rs + 16 * g, r + 4 * g, 32, hipMemcpyHostToDevice, st));
-      ZKP_HIP(hipMemcpyAsync(rs + 16 * g + 8, s + 4 * g, 32, hipMemcpyHostToDevice, st));
-    }
-  }
-  if (!(part & 2)) return;
-  hipLaunchKernelGGL(scalar_tail_kernel<FrP>, dim3(G), dim3(64), 0, st, S + pk->nz * 8, rs, s_stride * 8);
+struct ProofJob {
+  const uint64_t* const* z = nullptr;          // G assignments, nz Fr (Montgomery) each
+  bool z_on_device = false;
+  const uint64_t *r = nullptr, *s = nullptr;   // proof g: r + 4 g, s + 4 g (host)
+  int G = 1;
+  // != nullptr (base-sharded key): no assembly; the 5 XYZZ sums of this rank's slices (A | B1 | B2 | H | L, G2-sized slots) are
+  // left there (device) for the all-gather
+  char* partial_out = nullptr;
+};
 
-  const MsmVtbl* v1 = msm_vtbl(pk->curve, 1);
-  const MsmVtbl* v2 = msm_vtbl(pk->curve, 2);
-  const size_t slot = v2->xyzz_bytes;                  // uniform slot size
-  char* res = reinterpret_cast<char*>(PL.results.get(6 * slot * G));    // proof g: slots 6 g .. 6 g + 5
-  const uint64_t* Sd = reinterpret_cast<const uint64_t*>(S);
-  bool l_done_in_fan = false, g2_done_in_fan = false, chained = false;
-  float acc_ms = 0.f, scan_ms = 0.f;
-  uint64_t ent = 0, scan_bytes = 0, scan_runs = 0;
-  // Schedule.  profiling: everything on the main stream, one MSM at a time, with per-phase events.
-  // otherwise: three streams —  main: witness_map -> H ;  ws1: A -> L ;  ws2: B1 -> B2  — joined before assembly.
-  // ZKP_SINGLE_STREAM=1: one stream per proof (no fan-out inside a proof); concurrency then comes from the lanes only
-  const zkp_tune& tune = ctx->tune;
-  const bool fan = !prof && !tune.single_stream;
-  uint32_t* h = nullptr;
-  size_t h_stride = 0;                               // scalars between the h vectors of two proofs of a group
-  auto witness_maps = [&]() {                        // one witness map per proof, each in its own abc region of the lane
-    h_stride = 3 * pk->N;
-    for (int g = 0; g < G; g++) {
-      uint32_t* hg = witness_map_dev<FrP>(ctx, pk, S + g * s_stride * 8, !pk->h_lagrange, g, G);
-      if (g == 0) h = hg;
-      ZKP_REQUIRE(hg == h + (size_t)g * h_stride * 8, ZKP_ERR_BAD_ARG);     // h sits at the same place in every region
-    }
-  };
-  // defer_reduce / acc_into: the L -> H bucket chain (MsmJob)
-  auto run = [&](int idx, uint64_t handle, const uint64_t* sc, size_t n, int w, int sort_src = -1, int l1_src = -1,
-                 bool defer_reduce = false, int acc_into = -1) {
-    float ms = 0.f, ms_sc = 0.f;
-    uint64_t e = 0;
-    static const char* const names[5] = {"A", "B1", "B2", "H", "L"};
-    ctx->tl_tag = names[idx];
-    tic();
-#ifdef ZKP_ABLATION   // timing ablation builds only (ZKP_BUILD_DEFS=-DZKP_ABLATION -> variants/<tag>/): WRONG proofs, never in the shipped library
-    ctx->dbg_skip_k8 = ((tune.debug_skip_k8_mask >> idx) & 1) && ctx->batch_mode;
-#endif
-    MsmJob job;
-    job.handle = handle;
-    job.scalars_dev = sc;
-    job.n = n;
-    job.montgomery = true;
-    job.out_dev_xyzz = res + idx * slot;
-    job.ms_accumulate = prof ? &ms : nullptr;
-    job.ms_scan = prof ? &ms_sc : nullptr;
-    job.n_entries = &e;
-    job.ws = fan ? w : 0;
-    job.sort_src = fan ? sort_src : -1;
-    job.l1_src = fan ? l1_src : -1;
-    job.sets = G;
-    job.set_stride = idx == 3 ? h_stride : s_stride;
-    job.out_stride = 6 * slot;
-    job.defer_reduce = defer_reduce;
-    job.acc_into = acc_into;
-    msm_run(ctx, job);
-    ctx->dbg_skip_k8 = false;
-    toc(&tm.ms_msm[idx]);
-    acc_ms += ms;
-    ent += e;
+// The four events of a profiled proof and the zkp_groth16_timing they fill.  Every member but add_msm is a no-op unless the
+// context profiles.
+struct PhaseTimer {
+  zkp_ctx* const ctx;
+  hipStream_t const st;
+  const bool on;
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};      // phase begin, phase end, proof begin, proof end
+  zkp_groth16_timing tm{};
+  PhaseTimer(zkp_ctx* ctx, hipStream_t st) : ctx(ctx), st(st), on(ctx->profiling) {}
+  PhaseTimer(const PhaseTimer&) = delete;
+  ~PhaseTimer() {                                               // on every exit path (msm_run may throw)
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  void start() {
+    if (!on) return;
+    for (hipEvent_t& x : e) ZKP_HIP(hipEventCreate(&x));
+    ZKP_HIP(hipEventRecord(e[2], st));
+  }
+  void tic() { if (on) ZKP_HIP(hipEventRecord(e[0], st)); }
+  void toc(float* dst) {
+    if (!on) return;
+    ZKP_HIP(hipEventRecord(e[1], st));
+    ZKP_HIP(hipEventSynchronize(e[1]));
+    ZKP_HIP(hipEventElapsedTime(dst, e[0], e[1]));
+  }
+  // one MSM over n scalars: milliseconds of its accumulate kernel and of its scalar scan (0 where not measured), entries it sorted
+  void add_msm(int idx, size_t n, float ms, float ms_scan, uint64_t entries) {
+    tm.ms_msm_accumulate += ms;
+    tm.msm_points += entries;
     tm.ms_msm_acc[idx] = ms;
-    tm.msm_entries[idx] = e;
-    if (ms_sc > 0.f) {                       // algorithmic bytes of the scalar scan: scalars read by both passes + one 8-B word per entry
-      scan_ms += ms_sc;
-      scan_bytes += 2 * 32 * (uint64_t)n + 8 * e;
-      scan_runs += 1;
+    tm.msm_entries[idx] = entries;
+    if (ms_scan > 0.f) {                     // algorithmic bytes of the scalar scan: scalars read by both passes + one 8-B word per entry
+      tm.ms_msm_scan += ms_scan;
+      tm.msm_scan_bytes += 2 * 32 * (uint64_t)n + 8 * entries;
+      tm.msm_scan_launches += 1;
     }
     tm.msm_accumulate_launches += 1;
-  };
-  ctx->tl_tag.clear();
-  ctx->mark(st, "start");
-  if (fan) {
-    ZKP_HIP(hipEventRecord(ctx->cur->ev_fork, st));                       // S is complete
-    for (int w = 1; w < zkp_ctx::N_WS; w++) ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[w].stream, ctx->cur->ev_fork, 0));
+  }
+  void finish() {
+    if (!on) return;
+    ZKP_HIP(hipEventRecord(e[3], st));
+    ZKP_HIP(hipStreamSynchronize(st));
+    ZKP_HIP(hipEventElapsedTime(&tm.ms_total, e[2], e[3]));
+    ctx->last_timing = tm;
+  }
+};
+
+// One ProofJob on the current lane (ctx->cur), phase by phase in launch order: everything is asynchronous up to and including the
+// read-back of the 3 proof points into the lane's pinned host buffer; prove_finish() synchronises the lane and hands them out.
+// Schedule.  profiling: everything on the main stream, one MSM at a time, with per-phase events (plan_serial).
+// otherwise: the main stream (witness_map -> H) and the three workspace streams of the lane, forked after the scalar tail and joined
+// before assembly (plan_round2, or plan_round1 with ZKP_LATENCY_PLAN=0).
+// ZKP_SINGLE_STREAM=1: one stream per proof (no fan-out inside a proof); concurrency then comes from the lanes only
+struct ProofRun {
+  zkp_ctx* const ctx;
+  zkp_groth16_pk* const pk;
+  const ProofJob& job;
+  zkp_lane* const lane;
+  hipStream_t const st;
+  const zkp_tune& tune;
+  const MsmVtbl *const v1, *const v2;
+  const ProofWords pw;
+  const int G;
+  const size_t slot;                   // uniform (G2-sized) result slot; proof g: slots 6 g .. 6 g + 5 (A, B1, B2, H, L, then T / C)
+  const size_t s_stride, h_stride;     // scalars between the S / the h vectors of two proofs of a group
+  const bool fan;                      // the proof fans out over the lane's workspace streams
+  // zkp_ctx_config.host_affine = ZKP_OFF / ZKP_HOST_AFFINE=0: into_affine of the proof points on the device (rounds 1-3) instead of the host
+  const bool host_tail;
+  uint32_t* const S;
+  const LaneProofBuf buf;
+  char* const res;
+  PhaseTimer timer;
+  // what a phase leaves for the phases behind it
+  uint32_t* h = nullptr;               // the witness map's output of proof 0 (proof g: h_stride scalars behind proof g - 1)
+  bool l_done = false, g2_done = false, part1_done = false;     // the plan has run the L MSM / proof.b's into_affine / assembly part 1
+  bool chained = false;                // L's buckets stay in workspace 1 for H to reduce with its own
+
+  static const ProofJob& checked(zkp_ctx* ctx, const zkp_groth16_pk* pk, const ProofJob& job) {
+    ZKP_REQUIRE((pk->shard_world > 0) == (job.partial_out != nullptr), ZKP_ERR_BAD_ARG);
+    ZKP_REQUIRE(pk->hA != 0, ZKP_ERR_BAD_ARG);             // matrices-only key: use the sharded path
+    ZKP_REQUIRE(job.G >= 1 && job.G <= zkp_lane::MAX_FUSE, ZKP_ERR_BAD_ARG);
+    const bool default_plan = !ctx->profiling && !ctx->tune.single_stream && ctx->tune.latency_plan != 0;
+    ZKP_REQUIRE(job.G == 1 || (job.z && !job.partial_out && default_plan), ZKP_ERR_BAD_ARG);
+    return job;
+  }
+  ProofRun(zkp_ctx* ctx, zkp_groth16_pk* pk, const ProofJob& j)
+      : ctx(ctx), pk(pk), job(checked(ctx, pk, j)), lane(ctx->cur), st(lane->stream), tune(ctx->tune), v1(msm_vtbl(pk->curve, 1)),
+        v2(msm_vtbl(pk->curve, 2)), pw(pk->curve), G(job.G), slot(v2->xyzz_bytes), s_stride(pk->nz + 4), h_stride(3 * pk->N),
+        fan(!ctx->profiling && !tune.single_stream), host_tail(ctx->cfg.host_affine && !job.partial_out),
+        S(pk->lane[ctx->cur_idx].S.as<uint32_t>(s_stride * 8 * G)), buf(pk->lane[ctx->cur_idx].proof, G),
+        res(reinterpret_cast<char*>(pk->lane[ctx->cur_idx].results.get(6 * slot * G))), timer(ctx, st) {
+    timer.start();
+  }
+
+  // z, r, s into the lane's buffers: all that runs in front of a graph launch
+  void copy_inputs() {
+    const hipMemcpyKind z_kind = job.z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (int g = 0; g < G; g++) {
+      ZKP_HIP(hipMemcpyAsync(S + g * s_stride * 8, job.z[g], pk->nz * 32, z_kind, st));
+      ZKP_HIP(hipMemcpyAsync(buf.rs + RS_STEP * g, job.r + 4 * g, 32, hipMemcpyHostToDevice, st));
+      ZKP_HIP(hipMemcpyAsync(buf.rs + RS_STEP * g + 8, job.s + 4 * g, 32, hipMemcpyHostToDevice, st));
+    }
+  }
+
+  // everything behind the inputs: what a hipGraph captures
+  void enqueue() {
+    with_fr(pk->curve, [&](auto P) {
+      hipLaunchKernelGGL(scalar_tail_kernel<decltype(P)>, dim3(G), dim3(64), 0, st, S + pk->nz * 8, buf.rs, s_stride * 8);
+    });
+    ctx->tl_tag.clear();
+    ctx->mark(st, "start");
+    if (fan) fork();
     // The witness map heads the longest chain of a proof (witness map -> H MSM -> assembly): its launches go out FIRST, before
     // the ~150 launches of the four other MSMs (0.5 ms of host time): single-proof latency 10.1 -> 9.65 ms (ZKP_WM_FIRST=0: after
     // them, as in round 1).  Making the other MSMs' accumulate kernels wait for it — a kernel timeline shows machine-filling
     // accumulates from three streams leaving its kernels few wave slots for milliseconds — was measured too: 10.3 ms, not kept.
-    if (tune.wm_first) {
-      witness_maps();
-      ctx->mark(st, "wm");
-    }
+    const bool wm_first = !fan || tune.wm_first;       // (the serial plan always maps first)
+    if (wm_first) witness_maps();
+    if (wm_first && fan) ctx->mark(st, "wm");
     // (Round 4, measured with ZKP_TIMELINE=1 and removed again: holding the accumulate kernels of A / B1 / B2 / L until the witness map
     //  is done — the map ends at 5.4 ms of an 8.2 ms proof when they start at 0.9 ms — and giving L a workspace of its own so that its
     //  accumulate need not wait for A's reduction chain: 8.6-8.8 / 8.6-8.9 / 9.3-9.6 ms (gate / workspace / both) against 8.0-8.4.  The
     //  machine-filling accumulates only change places; what ends last is still one accumulate + its reduction.  A third plan — main: map ->
     //  H (sorted, accumulated, reduction deferred) -> L on top of H's buckets; B2 at once; A / B1 accumulates held until H is sorted —
     //  proved correct and ran 9.2-9.7 ms.  profiles/r04_latency_experiments.txt.)
-    const bool l_own = tune.l_own_stream;
-    (void)latency_plan;
-    const bool lat = tune.latency_plan >= 0 ? tune.latency_plan != 0 : true;
-    ZKP_REQUIRE(G == 1 || lat, ZKP_ERR_BAD_ARG);
-    if (lat) {
-      // Stream plan (round 2; default for single proofs AND the pipelined batch — measured 113.6 vs 111.2 proofs/s and 11.0 vs
-      // 11.9 ms single-proof latency against the round-1 plan below, which ZKP_LATENCY_PLAN=0 restores):
-      //   ws2: B2 | ws1: A -> L | ws3: B1 (B2's sort), then s*g_a + r*g1_b as soon as A exists | main: witness_map -> H
-      // (A is enqueued first: with a shared level-1 pass B2's stream waits on an event that A's stream must have recorded)
-      const int l1 = pk->share_l1 ? 1 : -1;
-      const bool b_l1 = pk->share_l1 && pk->b_in_l1;
-      if (!b_l1) run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 2);
-      run(0, pk->hA, Sd + 4 * pk->q_lo[0], pk->q_n[0], 1);
-      ZKP_HIP(hipEventRecord(ctx->cur->ev_a, ctx->cur->ws[1].stream));
-      if (b_l1) run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 2, -1, l1);
-      // proof.b needs B2 only: its into_affine runs on B2's stream as soon as the MSM is done instead of in the tail of the proof
-      if (!partial_out && tune.g2_early && !host_tail) {
-        v2->assemble_g2(ctx->cur->ws[2].stream, res, slot, proof_dev, flags_dev, 2 * v1->fN, G);
-        g2_done_in_fan = true;
-      }
-      run(1, pk->hB1, Sd + 4 * pk->q_lo[1], pk->q_n[1], 3, pk->share_b_sort ? 2 : -1);
-      chained = pk->chain_lh;                          // L's buckets stay in workspace 1 for H to reduce with its own
-      run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 1, pk->share_al_sort ? 1 : -1, l1, chained);   // A's sort / level-1 pass, still in this workspace
-      if (!partial_out) {
-        ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[3].stream, ctx->cur->ev_a, 0));
-        v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, G);
-        ctx->tl_tag.clear();
-        ctx->mark(ctx->cur->ws[3].stream, "part1");
-      }
+    if (!fan) plan_serial();
+    else if (tune.latency_plan != 0) plan_round2();
+    else plan_round1();
+    if (!wm_first) witness_maps();
+    // chained: on top of L's buckets (workspace 1): result slot 3 = h_acc + l', slot 4 = identity
+    msm(3, 0, -1, -1, false, chained ? 1 : -1);        // prover.rs:186-187 (min(len) truncation in q_n)
+    if (!l_done) msm(4, 0);                            // prover.rs:189-190
+    if (fan) join();
+    if (job.partial_out) {
+      emit_partials();
     } else {
-    // stream plan (longest chain first): ws2: B2 | ws1: A -> B1 | main: witness_map -> H | ws3: L, then part 1 after A, B1
-    // (4 lanes x 4 streams = 16 streams)
-    run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 2);                          // prover.rs:182-184
-    run(0, pk->hA, Sd + 4 * pk->q_lo[0], pk->q_n[0], 1);                           // prover.rs:164-167
-    run(1, pk->hB1, Sd + 4 * pk->q_lo[1], pk->q_n[1], 1, pk->share_b_sort ? 2 : -1);   // prover.rs:170-177 (B2's bucket sort reused)
-    // (A's sort is reused only when B1 does not re-sort on the same workspace in the meantime, i.e. when B1 takes B2's sort)
-    if (l_own) run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 3, pk->share_al_sort && pk->share_b_sort ? 1 : -1);   // prover.rs:189-190
-    ZKP_HIP(hipEventRecord(ctx->cur->ev_b1, ctx->cur->ws[1].stream));
-    // the two dynamic scalar multiplications (s*g_a, r*g1_b) are a ~2 ms single-lane chain each: start them as soon as
-    // A and B1 exist so they hide under the remaining MSMs
-    if (!partial_out) {
-      ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[3].stream, ctx->cur->ev_b1, 0));
-      v1->assemble_g1_part1(ctx->cur->ws[3].stream, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, 1);
+      assemble();
+      read_back();
     }
-    }
-    l_done_in_fan = lat || l_own;
-  }
-  ZKP_REQUIRE(G == 1 || fan, ZKP_ERR_BAD_ARG);
-  tic();
-  if (!h) witness_maps();
-  toc(&tm.ms_witness_map);
-  if (!fan) {
-    run(0, pk->hA, Sd + 4 * pk->q_lo[0], pk->q_n[0], 0);
-    run(1, pk->hB1, Sd + 4 * pk->q_lo[1], pk->q_n[1], 0);
-    run(2, pk->hB2, Sd + 4 * pk->q_lo[2], pk->q_n[2], 0);
-  }
-  // chained: on top of L's buckets (workspace 1): result slot 3 = h_acc + l', slot 4 = identity
-  run(3, pk->hH, reinterpret_cast<const uint64_t*>(h) + 4 * pk->q_lo[3], pk->q_n[3], 0, -1, -1, false, chained ? 1 : -1);  // :186-187 (min(len) truncation in q_n)
-  if (!(fan && l_done_in_fan)) run(4, pk->hL, Sd + 4 * pk->q_lo[4], pk->q_n[4], 0);                                 // :189-190
-  if (fan) {
-    for (int w = 1; w < zkp_ctx::N_WS; w++) {
-      ZKP_HIP(hipEventRecord(ctx->cur->ws[w].done, ctx->cur->ws[w].stream));
-      ZKP_HIP(hipStreamWaitEvent(st, ctx->cur->ws[w].done, 0));
-    }
-  }
-  tm.ms_msm_accumulate = acc_ms;
-  tm.msm_points = ent;
-  tm.ms_msm_scan = scan_ms;
-  tm.msm_scan_bytes = scan_bytes;
-  tm.msm_scan_launches = scan_runs;
-  if (partial_out) {
-    ZKP_HIP(hipMemcpyAsync(partial_out, res, 5 * slot, hipMemcpyDeviceToDevice, st));
-    ZKP_HIP(hipGetLastError());
-    if (prof) {
-      ZKP_HIP(hipEventRecord(eT1, st));
-      ZKP_HIP(hipStreamSynchronize(st));
-      ZKP_HIP(hipEventElapsedTime(&tm.ms_total, eT0, eT1));
-      ctx->last_timing = tm;
-    }
-    return;
+    timer.finish();
   }
 
-  tic();
-  // proof layout (32-bit words): A = 2*fN1 | B = 2*fN2 | C = 2*fN1
-  if (!fan) v1->assemble_g1_part1(st, res, slot, rs, host_tail ? nullptr : proof_dev, flags_dev, 1);
-  v1->assemble_g1_part2(st, res, slot, host_tail ? nullptr : proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN, G);
-  if (!g2_done_in_fan && !host_tail) v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN, G);
-  ZKP_HIP(hipGetLastError());
-  toc(&tm.ms_assemble);
-  const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
-  for (int g = 0; g < G; g++) {                              // proof g lands HOST_PROOF_WORDS words behind proof g - 1
-    uint32_t* hp = ctx->cur->host_proof + (size_t)g * zkp_lane::HOST_PROOF_WORDS;
-    const char* rg = res + (size_t)g * 6 * slot;
-    if (host_tail) {
-      // the three proof points go back as XYZZ (A = slot 0, B = slot 2, C = slot 5); prove_finish makes them affine on the host
-      // with one inversion (host_field.hpp) — three single-lane Fermat chains (0.25-0.32 ms each) leave the tail of the proof
-      ZKP_HIP(hipMemcpyAsync(hp, rg, 16 * (size_t)v1->fN, hipMemcpyDeviceToHost, st));
-      ZKP_HIP(hipMemcpyAsync(hp + 4 * v1->fN, rg + 2 * slot, 16 * (size_t)v2->fN, hipMemcpyDeviceToHost, st));
-      ZKP_HIP(hipMemcpyAsync(hp + 4 * v1->fN + 4 * v2->fN, rg + 5 * slot, 16 * (size_t)v1->fN, hipMemcpyDeviceToHost, st));
-    } else {
-      ZKP_HIP(hipMemcpyAsync(hp, proof_dev + (size_t)g * ASM_OUT_STEP, proof_words * 4, hipMemcpyDeviceToHost, st));
-      ZKP_HIP(hipMemcpyAsync(hp + 256, flags_dev + 4 * g, 12, hipMemcpyDeviceToHost, st));
+  void fork() {
+    ZKP_HIP(hipEventRecord(lane->ev_fork, st));                       // S is complete
+    for (int w = 1; w < zkp_ctx::N_WS; w++) ZKP_HIP(hipStreamWaitEvent(lane->ws[w].stream, lane->ev_fork, 0));
+  }
+  void join() {
+    for (int w = 1; w < zkp_ctx::N_WS; w++) {
+      ZKP_HIP(hipEventRecord(lane->ws[w].done, lane->ws[w].stream));
+      ZKP_HIP(hipStreamWaitEvent(st, lane->ws[w].done, 0));
     }
   }
-  ctx->tl_tag.clear();
-  ctx->mark(st, "copied");
-  ctx->cur->host_tail = host_tail;
-  ctx->cur->busy = true;
-  ctx->cur->group = G;
-  if (prof) {
-    ZKP_HIP(hipEventRecord(eT1, st));
-    ZKP_HIP(hipStreamSynchronize(st));
-    ZKP_HIP(hipEventElapsedTime(&tm.ms_total, eT0, eT1));
-    ctx->last_timing = tm;
+
+  // one witness map per proof on the main stream, each in its own abc region of the lane
+  void witness_maps() {
+    timer.tic();
+    with_fr(pk->curve, [&](auto P) {
+      for (int g = 0; g < G; g++) {
+        uint32_t* hg = witness_map_dev<decltype(P)>(ctx, pk, S + g * s_stride * 8, !pk->h_lagrange, g, G);
+        if (g == 0) h = hg;
+        ZKP_REQUIRE(hg == h + (size_t)g * h_stride * 8, ZKP_ERR_BAD_ARG);     // h sits at the same place in every region
+      }
+    });
+    timer.toc(&timer.tm.ms_witness_map);
   }
+
+  // MSM idx (0..4: A, B1, B2, H, L) into result slot idx, on workspace ws of the lane and its stream (0: the main stream).
+  // sort_src / l1_src: the workspace whose bucket sort / level-1 pass it reuses; defer / acc_into: the L -> H bucket chain (MsmJob)
+  void msm(int idx, int ws, int sort_src = -1, int l1_src = -1, bool defer = false, int acc_into = -1) {
+    static const char* const names[5] = {"A", "B1", "B2", "H", "L"};
+    const uint64_t handles[5] = {pk->hA, pk->hB1, pk->hB2, pk->hH, pk->hL};
+    const bool on_h = idx == 3;                          // H runs over the witness map's output, the others over slices of S
+    float ms = 0.f, ms_scan = 0.f;
+    uint64_t entries = 0;
+    ctx->tl_tag = names[idx];
+    timer.tic();
+#ifdef ZKP_ABLATION   // timing ablation builds only (ZKP_BUILD_DEFS=-DZKP_ABLATION -> variants/<tag>/): WRONG proofs, never in the shipped library
+    ctx->dbg_skip_k8 = ((tune.debug_skip_k8_mask >> idx) & 1) && ctx->batch_mode;
+#endif
+    MsmJob m;
+    m.handle = handles[idx];
+    m.scalars_dev = reinterpret_cast<const uint64_t*>(on_h ? h : S) + 4 * pk->q_lo[idx];
+    m.n = pk->q_n[idx];
+    m.montgomery = true;
+    m.out_dev_xyzz = res + idx * slot;
+    m.ms_accumulate = timer.on ? &ms : nullptr;
+    m.ms_scan = timer.on ? &ms_scan : nullptr;
+    m.n_entries = &entries;
+    m.ws = ws;
+    m.sort_src = sort_src;
+    m.l1_src = l1_src;
+    m.sets = G;
+    m.set_stride = on_h ? h_stride : s_stride;
+    m.out_stride = 6 * slot;
+    m.defer_reduce = defer;
+    m.acc_into = acc_into;
+    msm_run(ctx, m);
+    ctx->dbg_skip_k8 = false;
+    timer.toc(&timer.tm.ms_msm[idx]);
+    timer.add_msm(idx, m.n, ms, ms_scan, entries);
+  }
+
+  // Stream plan (round 2; default for single proofs AND the pipelined batch — measured 113.6 vs 111.2 proofs/s and 11.0 vs
+  // 11.9 ms single-proof latency against the round-1 plan below, which ZKP_LATENCY_PLAN=0 restores):
+  //   ws2: B2 | ws1: A -> L | ws3: B1 (B2's sort), then s*g_a + r*g1_b as soon as A exists | main: witness_map -> H
+  // (A is enqueued first: with a shared level-1 pass B2's stream waits on an event that A's stream must have recorded)
+  void plan_round2() {
+    const int l1 = pk->share_l1 ? 1 : -1;
+    const bool b_l1 = pk->share_l1 && pk->b_in_l1;
+    if (!b_l1) msm(2, 2);
+    msm(0, 1);
+    ZKP_HIP(hipEventRecord(lane->ev_a, lane->ws[1].stream));
+    if (b_l1) msm(2, 2, -1, l1);
+    // proof.b needs B2 only: its into_affine runs on B2's stream as soon as the MSM is done instead of in the tail of the proof
+    if (!job.partial_out && tune.g2_early && !host_tail) {
+      v2->assemble_g2(lane->ws[2].stream, res, slot, buf.proof, buf.flags, pw.b_off(), G);
+      g2_done = true;
+    }
+    msm(1, 3, pk->share_b_sort ? 2 : -1);
+    chained = pk->chain_lh;
+    msm(4, 1, pk->share_al_sort ? 1 : -1, l1, chained);   // A's sort / level-1 pass, still in this workspace
+    l_done = true;
+    if (!job.partial_out) {
+      ZKP_HIP(hipStreamWaitEvent(lane->ws[3].stream, lane->ev_a, 0));
+      v1->assemble_g1_part1(lane->ws[3].stream, res, slot, buf.rs, host_tail ? nullptr : buf.proof, buf.flags, G);
+      part1_done = true;
+      ctx->tl_tag.clear();
+      ctx->mark(lane->ws[3].stream, "part1");
+    }
+  }
+
+  // Stream plan of round 1 (longest chain first): ws2: B2 | ws1: A -> B1 | main: witness_map -> H | ws3: L, then part 1 after A, B1
+  // (4 lanes x 4 streams = 16 streams).  ZKP_L_OWN_STREAM=0: L behind H on the main stream.
+  void plan_round1() {
+    msm(2, 2);                                         // prover.rs:182-184
+    msm(0, 1);                                         // prover.rs:164-167
+    msm(1, 1, pk->share_b_sort ? 2 : -1);              // prover.rs:170-177 (B2's bucket sort reused)
+    // (A's sort is reused only when B1 does not re-sort on the same workspace in the meantime, i.e. when B1 takes B2's sort)
+    if (tune.l_own_stream) {
+      msm(4, 3, pk->share_al_sort && pk->share_b_sort ? 1 : -1);     // prover.rs:189-190
+      l_done = true;
+    }
+    ZKP_HIP(hipEventRecord(lane->ev_b1, lane->ws[1].stream));
+    // the two dynamic scalar multiplications (s*g_a, r*g1_b) are a ~2 ms single-lane chain each: start them as soon as
+    // A and B1 exist so they hide under the remaining MSMs
+    if (!job.partial_out) {
+      ZKP_HIP(hipStreamWaitEvent(lane->ws[3].stream, lane->ev_b1, 0));
+      v1->assemble_g1_part1(lane->ws[3].stream, res, slot, buf.rs, host_tail ? nullptr : buf.proof, buf.flags, G);
+      part1_done = true;
+    }
+  }
+
+  // profiling or ZKP_SINGLE_STREAM=1: the z-MSMs one after the other on the main stream, behind the witness map; H, L and both
+  // parts of the assembly follow there
+  void plan_serial() {
+    msm(0, 0);
+    msm(1, 0);
+    msm(2, 0);
+  }
+
+  void emit_partials() {
+    ZKP_HIP(hipMemcpyAsync(job.partial_out, res, 5 * slot, hipMemcpyDeviceToDevice, st));
+    ZKP_HIP(hipGetLastError());
+  }
+
+  // what the plan has left of the assembly, on the main stream
+  void assemble() {
+    uint32_t* out = host_tail ? nullptr : buf.proof;     // host tail: the points stay XYZZ in their result slots
+    timer.tic();
+    if (!part1_done) v1->assemble_g1_part1(st, res, slot, buf.rs, out, buf.flags, G);
+    v1->assemble_g1_part2(st, res, slot, out, buf.flags, pw.c_off(), G);
+    if (!g2_done && !host_tail) v2->assemble_g2(st, res, slot, buf.proof, buf.flags, pw.b_off(), G);
+    ZKP_HIP(hipGetLastError());
+    timer.toc(&timer.tm.ms_assemble);
+  }
+
+  // the group's proofs into the lane's pinned landing zones; the lane is busy until prove_finish
+  void read_back() {
+    for (int g = 0; g < G; g++) {
+      const HostProofZone hz(lane, g, pw);
+      const char* rg = res + (size_t)g * 6 * slot;
+      if (host_tail) {
+        // the three proof points go back as XYZZ (A = slot 0, B = slot 2, C = slot 5); prove_finish makes them affine on the host
+        // with one inversion (host_field.hpp) — three single-lane Fermat chains (0.25-0.32 ms each) leave the tail of the proof
+        ZKP_HIP(hipMemcpyAsync(hz.a, rg, 16 * pw.fN1, hipMemcpyDeviceToHost, st));
+        ZKP_HIP(hipMemcpyAsync(hz.b, rg + 2 * slot, 16 * pw.fN2, hipMemcpyDeviceToHost, st));
+        ZKP_HIP(hipMemcpyAsync(hz.c, rg + 5 * slot, 16 * pw.fN1, hipMemcpyDeviceToHost, st));
+      } else {
+        ZKP_HIP(hipMemcpyAsync(hz.base, buf.proof + (size_t)g * ASM_OUT_STEP, pw.affine() * 4, hipMemcpyDeviceToHost, st));
+        ZKP_HIP(hipMemcpyAsync(hz.flags, buf.flags + FLAG_STEP * g, 12, hipMemcpyDeviceToHost, st));
+      }
+    }
+    ctx->tl_tag.clear();
+    ctx->mark(st, "copied");
+    lane->host_tail = host_tail;
+    lane->busy = true;
+    lane->group = G;
+  }
+};
+
+static void prove_enqueue_eager(zkp_ctx* ctx, zkp_groth16_pk* pk, const ProofJob& job) {
+  ProofRun run(ctx, pk, job);
+  run.copy_inputs();
+  run.enqueue();
 }
 
 // every device pointer a captured proof embeds: if any scratch buffer was reallocated since the capture (another, larger
@@ -1048,34 +1176,35 @@ static std::vector<const void*> lane_signature(zkp_ctx* ctx, zkp_groth16_pk* pk)
 
 // One proof on the current lane.  With ZKP_GRAPH=1 the ~250 launches of a proof (4 streams, fork/join by events) are
 // captured once per (key, lane) into a hipGraph and replayed; the inputs are copied in front of the graph launch.
-template <class FrP>
-static void prove_enqueue(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
-                          const uint64_t* s, bool latency_plan = false) {
+// Lane states: 0 = never run, 1 = ran eagerly once (scratch allocated, signature recorded), 2 = captured.
+static void prove_enqueue(zkp_ctx* ctx, zkp_groth16_pk* pk, const ProofJob& job) {
   if (!ctx->tune.graph || ctx->profiling || ctx->tune.single_stream) {
-    prove_enqueue_part<FrP>(ctx, pk, z, z_on_device, r, s, 3, nullptr, latency_plan);
+    prove_enqueue_eager(ctx, pk, job);
     return;
   }
-  // (graph replay always uses the throughput plan: a captured graph embeds its stream plan)
+  ZKP_REQUIRE(job.G == 1, ZKP_ERR_BAD_ARG);
   zkp_groth16_pk::PerLane& PL = pk->lane[ctx->cur_idx];
   hipStream_t st = ctx->cur->stream;
-  if (PL.graph_state == 2 && PL.sig == lane_signature(ctx, pk)) {
-    prove_enqueue_part<FrP>(ctx, pk, z, z_on_device, r, s, 1);
-    ZKP_HIP(hipGraphLaunch(PL.graph_exec, st));
-    ctx->cur->busy = true;
-    return;
-  }
-  if (PL.graph_state == 2) {                              // stale
+  const bool current = PL.graph_state != 0 && PL.sig == lane_signature(ctx, pk);
+  if (PL.graph_state == 2 && !current) {                   // stale
     (void)hipGraphExecDestroy(PL.graph_exec);
     (void)hipGraphDestroy(PL.graph);
     PL.graph_exec = nullptr;
     PL.graph = nullptr;
     PL.graph_state = 0;
   }
-  if (PL.graph_state == 1 && PL.sig == lane_signature(ctx, pk)) {
-    prove_enqueue_part<FrP>(ctx, pk, z, z_on_device, r, s, 1);
+  if (PL.graph_state == 0 || !current) {
+    prove_enqueue_eager(ctx, pk, job);                     // allocates every scratch buffer
+    PL.sig = lane_signature(ctx, pk);
+    PL.graph_state = 1;
+    return;
+  }
+  ProofRun run(ctx, pk, job);
+  run.copy_inputs();
+  if (PL.graph_state == 1) {
     ZKP_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
     try {
-      prove_enqueue_part<FrP>(ctx, pk, z, z_on_device, r, s, 2);
+      run.enqueue();
     } catch (...) {
       hipGraph_t g = nullptr;
       (void)hipStreamEndCapture(st, &g);
@@ -1085,19 +1214,13 @@ static void prove_enqueue(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, b
     ZKP_HIP(hipStreamEndCapture(st, &PL.graph));
     ZKP_HIP(hipGraphInstantiate(&PL.graph_exec, PL.graph, nullptr, nullptr, 0));
     PL.graph_state = 2;
-    ZKP_HIP(hipGraphLaunch(PL.graph_exec, st));
-    ctx->cur->busy = true;
-    return;
   }
-  prove_enqueue_part<FrP>(ctx, pk, z, z_on_device, r, s, 3);    // eager run: allocates every scratch buffer
-  PL.sig = lane_signature(ctx, pk);
-  PL.graph_state = 1;
+  ZKP_HIP(hipGraphLaunch(PL.graph_exec, st));
+  ctx->cur->busy = true;
 }
 
 static void prove_finish(zkp_ctx* ctx, zkp_groth16_pk* pk, uint64_t* proof_out, uint8_t* inf_out) {
-  const MsmVtbl* v1 = msm_vtbl(pk->curve, 1);
-  const MsmVtbl* v2 = msm_vtbl(pk->curve, 2);
-  const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
+  const ProofWords pw(pk->curve);
   ZKP_HIP(hipStreamSynchronize(ctx->cur->stream));
   if (!ctx->tl.empty()) {
     std::string line = "[zkp timeline ms]";
@@ -1116,18 +1239,35 @@ static void prove_finish(zkp_ctx* ctx, zkp_groth16_pk* pk, uint64_t* proof_out, 
   }
   // a fused group hands out its proofs one behind the other: they are consecutive proofs of the batch
   for (int g = 0; g < ctx->cur->group; g++) {
-    const uint32_t* hp = ctx->cur->host_proof + (size_t)g * zkp_lane::HOST_PROOF_WORDS;
-    uint32_t* po = reinterpret_cast<uint32_t*>(proof_out) + (size_t)g * proof_words;
+    const HostProofZone hz(ctx->cur, g, pw);
+    uint32_t* po = reinterpret_cast<uint32_t*>(proof_out) + (size_t)g * pw.affine();
     if (ctx->cur->host_tail) {
       const hostf::HostField Fq = hostf::fq_field(pk->curve);
-      hostf::groth16_points_into_affine(Fq, hp, hp + 4 * v1->fN, hp + 4 * v1->fN + 4 * v2->fN, po, inf_out + 3 * g);
+      hostf::groth16_points_into_affine(Fq, hz.a, hz.b, hz.c, po, inf_out + 3 * g);
     } else {
-      memcpy(po, hp, proof_words * 4);
-      for (int i = 0; i < 3; i++) inf_out[3 * g + i] = (uint8_t)hp[256 + i];
+      memcpy(po, hz.base, pw.affine() * 4);
+      for (int i = 0; i < 3; i++) inf_out[3 * g + i] = (uint8_t)hz.flags[i];
     }
   }
   ctx->cur->busy = false;
   ctx->cur->group = 1;
+}
+
+// the tail the two assembly entry points share: six result slots and [r, s] in `b` -> the proof and its flags on the host
+static void assemble_and_fetch(zkp_ctx* ctx, int curve, const AssembleBuf& b, size_t slot, uint64_t* proof_out, uint8_t* inf_out) {
+  const MsmVtbl* v1 = msm_vtbl(curve, 1);
+  const MsmVtbl* v2 = msm_vtbl(curve, 2);
+  const ProofWords pw(curve);
+  hipStream_t st = ctx->cur->stream;
+  v1->assemble_g1_part1(st, b.res, slot, b.rs, b.proof, b.flags, 1);
+  v1->assemble_g1_part2(st, b.res, slot, b.proof, b.flags, pw.c_off(), 1);
+  v2->assemble_g2(st, b.res, slot, b.proof, b.flags, pw.b_off(), 1);
+  ZKP_HIP(hipGetLastError());
+  uint32_t flags_host[FLAG_STEP] = {0, 0, 0, 0};
+  ZKP_HIP(hipMemcpyAsync(proof_out, b.proof, pw.affine() * 4, hipMemcpyDeviceToHost, st));
+  ZKP_HIP(hipMemcpyAsync(flags_host, b.flags, 12, hipMemcpyDeviceToHost, st));
+  ZKP_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < 3; i++) inf_out[i] = (uint8_t)flags_host[i];
 }
 
 void groth16_assemble(zkp_ctx* ctx, int curve, const uint64_t* sums, const uint64_t* r, const uint64_t* s,
@@ -1138,27 +1278,12 @@ void groth16_assemble(zkp_ctx* ctx, int curve, const uint64_t* sums, const uint6
   const size_t slot = v2->xyzz_bytes;
   const size_t j1 = 3 * (size_t)v1->fN, j2 = 3 * (size_t)v2->fN;          // words
   const size_t in_words = 4 * j1 + j2;
-  uint32_t* buf = ctx->msm_misc.as<uint32_t>(in_words + 16 + 6 * slot / 4 + 256 + 16);
-  uint32_t* jac = buf;
-  uint32_t* rs = jac + in_words;
-  char* res = reinterpret_cast<char*>(rs + 16);
-  uint32_t* proof_dev = reinterpret_cast<uint32_t*>(res + 6 * slot);
-  uint32_t* flags_dev = proof_dev + 240;
-  ZKP_HIP(hipMemcpyAsync(jac, sums, in_words * 4, hipMemcpyHostToDevice, st));
-  ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
-  ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
+  const AssembleBuf b(ctx, slot, in_words);
+  ZKP_HIP(hipMemcpyAsync(b.in, sums, in_words * 4, hipMemcpyHostToDevice, st));
+  b.upload_rs(st, r, s);
   const size_t off[5] = {0, j1, 2 * j1, 2 * j1 + j2, 3 * j1 + j2};
-  for (int i = 0; i < 5; i++) (i == 2 ? v2 : v1)->from_jacobian(st, jac + off[i], res + i * slot);
-  v1->assemble_g1_part1(st, res, slot, rs, proof_dev, flags_dev, 1);
-  v1->assemble_g1_part2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN, 1);
-  v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN, 1);
-  ZKP_HIP(hipGetLastError());
-  const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
-  uint32_t flags_host[4] = {0, 0, 0, 0};
-  ZKP_HIP(hipMemcpyAsync(proof_out, proof_dev, proof_words * 4, hipMemcpyDeviceToHost, st));
-  ZKP_HIP(hipMemcpyAsync(flags_host, flags_dev, 12, hipMemcpyDeviceToHost, st));
-  ZKP_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < 3; i++) inf_out[i] = (uint8_t)flags_host[i];
+  for (int i = 0; i < 5; i++) (i == 2 ? v2 : v1)->from_jacobian(st, b.in + off[i], b.res + i * slot);
+  assemble_and_fetch(ctx, curve, b, slot, proof_out, inf_out);
 }
 
 size_t groth16_partials_bytes(int curve) { return 5 * msm_vtbl(curve, 2)->xyzz_bytes; }
@@ -1170,8 +1295,13 @@ void groth16_prove_partials(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z_
   ZKP_REQUIRE(pk->shard_world > 0, ZKP_ERR_BAD_ARG);
   ctx->cur = &ctx->lanes[0];
   ctx->cur_idx = 0;
-  if (pk->curve == ZKP_BN254) prove_enqueue_part<Bn254Fr>(ctx, pk, z_dev, true, r, s, 3, (char*)out_dev, true);
-  else prove_enqueue_part<Bls381Fr>(ctx, pk, z_dev, true, r, s, 3, (char*)out_dev, true);
+  ProofJob job;
+  job.z = &z_dev;
+  job.z_on_device = true;
+  job.r = r;
+  job.s = s;
+  job.partial_out = (char*)out_dev;
+  prove_enqueue_eager(ctx, pk, job);
   ZKP_HIP(hipStreamSynchronize(ctx->cur->stream));
 }
 
@@ -1184,25 +1314,11 @@ void groth16_fold_assemble(zkp_ctx* ctx, int curve, const void* gathered_dev, in
   const MsmVtbl* v2 = msm_vtbl(curve, 2);
   hipStream_t st = ctx->cur->stream;
   const size_t slot = v2->xyzz_bytes;
-  uint32_t* buf = ctx->msm_misc.as<uint32_t>(16 + 6 * slot / 4 + 256 + 16);
-  uint32_t* rs = buf;
-  char* res = reinterpret_cast<char*>(rs + 16);
-  uint32_t* proof_dev = reinterpret_cast<uint32_t*>(res + 6 * slot);
-  uint32_t* flags_dev = proof_dev + 240;
-  ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
-  ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
-  v1->fold_slots(st, (const char*)gathered_dev, 5 * slot, world, slot, 0x1b, res);     // A, B1, H, L
-  v2->fold_slots(st, (const char*)gathered_dev, 5 * slot, world, slot, 0x04, res);     // B2
-  v1->assemble_g1_part1(st, res, slot, rs, proof_dev, flags_dev, 1);
-  v1->assemble_g1_part2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN + 2 * v2->fN, 1);
-  v2->assemble_g2(st, res, slot, proof_dev, flags_dev, 2 * v1->fN, 1);
-  ZKP_HIP(hipGetLastError());
-  const size_t proof_words = 4 * (size_t)v1->fN + 2 * (size_t)v2->fN;
-  uint32_t flags_host[4] = {0, 0, 0, 0};
-  ZKP_HIP(hipMemcpyAsync(proof_out, proof_dev, proof_words * 4, hipMemcpyDeviceToHost, st));
-  ZKP_HIP(hipMemcpyAsync(flags_host, flags_dev, 12, hipMemcpyDeviceToHost, st));
-  ZKP_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < 3; i++) inf_out[i] = (uint8_t)flags_host[i];
+  const AssembleBuf b(ctx, slot, 0);
+  b.upload_rs(st, r, s);
+  v1->fold_slots(st, (const char*)gathered_dev, 5 * slot, world, slot, 0x1b, b.res);     // A, B1, H, L
+  v2->fold_slots(st, (const char*)gathered_dev, 5 * slot, world, slot, 0x04, b.res);     // B2
+  assemble_and_fetch(ctx, curve, b, slot, proof_out, inf_out);
 }
 
 void groth16_prove(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
@@ -1211,8 +1327,12 @@ void groth16_prove(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_o
   ctx->cur = &ctx->lanes[0];
   ctx->cur_idx = 0;
   ctx->tl_on = ctx->tune.timeline && !ctx->profiling;
-  if (pk->curve == ZKP_BN254) prove_enqueue<Bn254Fr>(ctx, pk, z, z_on_device, r, s, true);
-  else prove_enqueue<Bls381Fr>(ctx, pk, z, z_on_device, r, s, true);
+  ProofJob job;
+  job.z = &z;
+  job.z_on_device = z_on_device;
+  job.r = r;
+  job.s = s;
+  prove_enqueue(ctx, pk, job);
   ctx->tl_on = false;
   prove_finish(ctx, pk, proof_out, inf_out);
 }
@@ -1220,7 +1340,7 @@ void groth16_prove(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_o
 // n proofs, software-pipelined over the lanes (8, or 4 above 2^22): group i+1 is enqueued before group i is awaited, so the
 // latency-bound tails (bucket reduction, assembly) of one overlap the throughput-bound kernels of the next.
 //
-// Fused groups.  ZKP_PROOF_FUSE (compile time, 1 or 2) consecutive proofs share ONE kernel chain (prove_enqueue_part G > 1): the
+// Fused groups.  ZKP_PROOF_FUSE (compile time, 1 or 2) consecutive proofs share ONE kernel chain (ProofJob G > 1): the
 // ~155 latency-bound launches of a proof (scans, task scheduling, pyramid tops, final sums, assembly) each use a sliver of the device
 // but hold a hardware queue while they run, and they last about as long for two proofs as for one.  A group runs on one lane with
 // that lane's four streams and the unchanged stream plan.  An odd remainder, profiling runs, ZKP_GRAPH=1, ZKP_SINGLE_STREAM=1,
@@ -1229,7 +1349,8 @@ void groth16_prove(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, bool z_o
 #ifndef ZKP_PROOF_FUSE
 #define ZKP_PROOF_FUSE 2
 #endif
-static_assert(ZKP_PROOF_FUSE == 1 || ZKP_PROOF_FUSE == 2, "group size: 1 or 2 (= zkp_lane::MAX_FUSE); larger groups are not tested");
+static_assert(ZKP_PROOF_FUSE == 1 || ZKP_PROOF_FUSE == 2, "group size: 1 or 2; larger groups are not tested");
+static_assert(ZKP_PROOF_FUSE <= zkp_lane::MAX_FUSE, "a lane's pinned landing zones hold MAX_FUSE proofs");
 void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint64_t* const* z_dev, const uint64_t* r,
                          const uint64_t* s, uint64_t* proofs_out, uint8_t* inf_out, bool z_on_device) {
   const MsmVtbl* v1 = msm_vtbl(pk->curve, 1);
@@ -1265,13 +1386,13 @@ void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint6
       if (!msm_sets_ok(ctx, hq, fuse)) fuse = 1;
   }
   auto enqueue = [&](size_t i, int G) {                      // proofs i .. i + G - 1 on the current lane
-    if (pk->curve == ZKP_BN254) {
-      if (G > 1) prove_enqueue_part<Bn254Fr>(ctx, pk, nullptr, z_on_device, r + 4 * i, s + 4 * i, 3, nullptr, false, G, z_dev + i);
-      else prove_enqueue<Bn254Fr>(ctx, pk, z_dev[i], z_on_device, r + 4 * i, s + 4 * i);
-    } else {
-      if (G > 1) prove_enqueue_part<Bls381Fr>(ctx, pk, nullptr, z_on_device, r + 4 * i, s + 4 * i, 3, nullptr, false, G, z_dev + i);
-      else prove_enqueue<Bls381Fr>(ctx, pk, z_dev[i], z_on_device, r + 4 * i, s + 4 * i);
-    }
+    ProofJob job;
+    job.z = z_dev + i;
+    job.z_on_device = z_on_device;
+    job.r = r + 4 * i;
+    job.s = s + 4 * i;
+    job.G = G;
+    prove_enqueue(ctx, pk, job);
   };
   try {
     // First pipelined batch of this key: a lane's scratch (bucket arrays, sort buffers, NTT scratch: GiBs at 2^22) is allocated
@@ -1823,8 +1944,7 @@ void groth16_prove_multi(zkp_ctx* root, zkp_groth16_pk_multi* M, const uint64_t*
                          const uint64_t* r, const uint64_t* s, uint64_t* proof_out, uint8_t* inf_out) {
   ZKP_REQUIRE(M->mode == 0 && M->pk.size() == root->devs.size() && !root->devs.empty(), ZKP_ERR_BAD_ARG);
   try {
-    if (M->curve == ZKP_BN254) prove_multi_t<Bn254Fr>(root, M, z, z_on_device, r, s, proof_out, inf_out);
-    else prove_multi_t<Bls381Fr>(root, M, z, z_on_device, r, s, proof_out, inf_out);
+    with_fr(M->curve, [&](auto P) { prove_multi_t<decltype(P)>(root, M, z, z_on_device, r, s, proof_out, inf_out); });
   } catch (...) {
     for (zkp_ctx* c : root->devs) {
       (void)hipSetDevice(c->device);

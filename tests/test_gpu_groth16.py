@@ -354,6 +354,78 @@ def test_schedule_switches_do_not_change_the_proof():
 
 
 
+# (public configuration, internal switches) of the schedule arms no other test reaches: the witness map behind the MSM launches, proof.b's
+# into_affine in the tail (on the host and on the device), the round-1 stream plan with L on its own stream and behind H, all of them
+_SCHEDULE_ARMS = {
+    "wm_last": ({}, {"ZKP_WM_FIRST": 0}),
+    "g2_late": ({}, {"ZKP_G2_EARLY": 0}),
+    "g2_late_device_affine": ({"host_affine": False}, {"ZKP_G2_EARLY": 0}),
+    "round1": ({}, {"ZKP_LATENCY_PLAN": 0}),
+    "round1_l_behind_h": ({}, {"ZKP_LATENCY_PLAN": 0, "ZKP_L_OWN_STREAM": 0}),
+    "all_flipped": ({}, {"ZKP_WM_FIRST": 0, "ZKP_G2_EARLY": 0, "ZKP_LATENCY_PLAN": 0}),
+}
+# entries (mixed additions) of the five MSMs A, B1, B2, H, L of this instance while profiling: measured with the parent commit's library
+_PROFILED_ENTRIES = {"bn254": [26509, 13273, 13273, 26591, 31804], "bls12_381": [26522, 13278, 13278, 26593, 31820]}
+
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
+def test_schedule_arms_and_profiling_do_not_change_the_proof(ctx, monkeypatch, curve):
+    """One blocking proof and a batch of 3 (one fused pair + a remainder) at domain 2^10 — all five MSMs non-empty, the full-table
+    NTT chain — are byte-identical, flags included, under every schedule arm above (each latched by a fresh context) and under
+    profiling (the serial plan with per-phase events), whose zkp_groth16_timing is checked field by field; a proof after profiling
+    is switched off again equals the baseline too.  BLS12-381 runs the round-1 arm and the profiling arm."""
+    import numpy as np
+    from ckb_zkp_amd.circuits import samples_for_domain
+    from tests.util import variant_ctx
+    inst = mimc_chain_instance(curve, samples_for_domain(10))
+    params = groth16.generate_parameters(ctx, curve, inst, **TOXIC)
+    c = params.curve
+    z = codec.fr_to_mont(inst.z, c).reshape(-1, 4)
+    rnd = random.Random(31)
+    rs = codec.fr_to_mont([rnd.randrange(c.r) for _ in range(3)], c)
+    ss = codec.fr_to_mont([rnd.randrange(c.r) for _ in range(3)], c)
+
+    def prove(x, pk):
+        zd = x.to_device(z)
+        try:
+            return pk.prove_raw(z, rs[0], ss[0]) + pk.prove_batch_raw([zd] * 3, rs, ss)
+        finally:
+            x.dev_free(zd)
+
+    def same(got, want):
+        return len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want))
+
+    with variant_ctx(monkeypatch, ctx.device, {}, {}) as v:
+        pk = groth16.ProvingKey(v, params, inst)
+        try:
+            assert pk.domain_size == 1 << 10
+            base = prove(v, pk)
+            assert np.array_equal(base[0], base[2][0]) and np.array_equal(base[1], base[3][0])
+            assert not base[1].any() and not base[3].any()
+            v.set_profiling(True)
+            try:
+                assert same(prove(v, pk), base)
+                t = pk.last_timing()
+            finally:
+                v.set_profiling(False)
+            print(curve, "profiled timing:", t)
+            assert t["msm_accumulate_launches"] == 5
+            assert t["msm_points"] == sum(t["msm_entries"])
+            assert all(ms > 0 for ms in t["ms_msm"]) and t["ms_witness_map"] > 0 and t["ms_assemble"] > 0 and t["ms_total"] > 0
+            assert t["msm_entries"] == _PROFILED_ENTRIES[curve]
+            assert same(prove(v, pk), base)
+        finally:
+            pk.free()
+    arms = _SCHEDULE_ARMS if curve == "bn254" else {"round1": _SCHEDULE_ARMS["round1"]}
+    for name, (config, env) in arms.items():
+        with variant_ctx(monkeypatch, ctx.device, config, env) as v:
+            pk = groth16.ProvingKey(v, params, inst)
+            try:
+                assert same(prove(v, pk), base), name
+            finally:
+                pk.free()
+
+
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
 def test_create_random_proof_and_no_zk_pass_the_reference_verifier(ctx, curve):
     """The reference's own round trip (groth16/tests/mini.rs:80-96): create_random_proof -> verify_proof == true, and
