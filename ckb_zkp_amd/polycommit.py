@@ -31,6 +31,7 @@ from .params import get_curve
 
 PEDERSEN_MAX_GENS = 1 << 16         # ZKP_PEDERSEN_MAX_GENS
 VECMAT_ROW_CHUNK = 32               # ZKP_FR_VECMAT_ROW_CHUNK
+PEDERSEN_ROW_LANES = 64             # csrc/pedersen.hpp PED_LANES: lane t of the row pass adds slices t, t + 64, ... of its row
 MAX_CELLS = 1 << 28                 # rows * cols of one zkp_pedersen_commit_rows_dev / zkp_fr_vecmat_dev call
 
 

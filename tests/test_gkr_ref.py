@@ -93,3 +93,25 @@ def test_layer_rules():
     with pytest.raises(ValueError, match="IllegalNode"):
         ref.Circuit(2, 2, [[(0, 0, 4)]])
     assert ref.eval_layer([(0, 0, 1), (1, 1, 1), (1, 0, 1)], [3, 5], 7) == [1, 4, 1, 0]
+
+
+@pytest.mark.parametrize("period", [7, 16])
+def test_periodic_round_helpers_equal_the_direct_sums(period):
+    """tests/util.periodic_round_sums / periodic_bind, on which the device tests of long tables rest, against the round functions of
+    gkr_ref and sumcheck_ref over the spelled-out tables (h = 32: four whole periods and four residues more, or two whole periods)"""
+    from tests import sumcheck_ref
+    from tests.util import periodic_bind, periodic_round_sums
+    r = get_curve("bn254").r
+    n = 64
+    bases = [rand_fr(r, period, 70 + s) for s in range(4)]
+    tables = [[b[j % period] for j in range(n)] for b in bases]
+    for phase, fu in ((1, None), (2, 12345)):
+        nt = 5 - phase
+        got = periodic_round_sums(lambda t: ref.round_evals(phase, t, fu, r), bases[:nt], n // 2, r)     # noqa: B023
+        assert got == ref.round_evals(phase, tables[:nt], fu, r)
+    for kind, arity in sumcheck_ref.ARITY.items():
+        got = periodic_round_sums(lambda t: sumcheck_ref.round_evals(kind, t, r), bases[:arity], n // 2, r)   # noqa: B023
+        assert got == sumcheck_ref.round_evals(kind, tables[:arity], r)
+    for b, t in zip(bases, tables):
+        block = periodic_bind(b, n // 2, 99, r)
+        assert [block[j % period] for j in range(n // 2)] == sumcheck_ref.combine_with_r(t, 99, r)

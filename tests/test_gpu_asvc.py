@@ -4,14 +4,15 @@ buffers are compared, and the inputs are read back unchanged.
 
 The sizes sit on the kernel chain's boundaries: the segment length L = 2^floor(log2 k) (k = 1, 2, 3, 4, 5 ...), L against ASVC_SPAN
 (k = 7, 8: the two forms of the output pass), the position group (ASVC_GROUP - 1 .. 2 ASVC_GROUP + 1), and n / L segments against
-one and two scan chunks (32, 64 segments) and one and two scan tiles (2^13, 2^14 segments)."""
+one and two scan chunks (32, 64 segments) and one and two scan tiles (2^13, 2^14 segments), and 2 ASVC_THREADS scan tiles (2^22
+segments: the second window of the top scan; 1.8 s on an MI355X's host, nearly all of it the 2^22 steps of the Python recursion)."""
 import random
 
 import numpy as np
 import pytest
 
 from ckb_zkp_amd import _lib, asvc, codec
-from ckb_zkp_amd.asvc import ASVC_CHUNK, ASVC_GROUP, ASVC_MAX_POSITIONS, ASVC_SPAN, ASVC_TILE
+from ckb_zkp_amd.asvc import ASVC_CHUNK, ASVC_GROUP, ASVC_MAX_POSITIONS, ASVC_SPAN, ASVC_THREADS, ASVC_TILE
 from ckb_zkp_amd.params import get_curve
 from oracle.pyref.curves import Group
 from tests import asvc_cases as cases
@@ -24,6 +25,7 @@ G = ASVC_GROUP
 GROUP_KS = [1, 2, G - 1, G, G + 1, 2 * G + 1]
 SPAN_KS = [ASVC_SPAN - 1, ASVC_SPAN, 2 * ASVC_SPAN + 1]
 assert ASVC_CHUNK == 32 and ASVC_TILE == 8192                     # the sizes below are poly.hip's, which the scan shares
+PERIOD = 4099                                                     # the 2^22 input repeats a block of this (prime) length
 
 
 def _bad(fn, status=-1):
@@ -165,6 +167,47 @@ def test_quotient_many_positions(ctx, curve, n, k):
     phi = [(x + (rng.randrange(c.r) if t < k else 0)) % c.r for t, x in enumerate(phi + [0] * (n - len(phi)))]
     got = device_quotient(ctx, c, phi, points)
     assert np.array_equal(got, codec.fr_to_mont(quo, c).reshape(n - k, 4))
+
+
+def test_quotient_two_windows_of_scan_tiles(ctx):
+    """n = 2^22 at k = 1 (L = 1: every coefficient is a segment): 2 ASVC_THREADS scan tiles, the smallest domain at which
+    asvc_scan_top_kernel takes a second window and the sum of the window above enters through `R * carry`.  The position is odd, so
+    w has order n and r^TILE = w^TILE is no small root of unity: a wrong carry power changes the result.  The input repeats a block
+    of prime length, encoded once and spread by indexing; the reference is q[t] = phi[t + 1] + w q[t + 1] on the Montgomery words
+    themselves (the recursion is linear, so it holds for q R), which saves a second conversion of 2^22 elements.  The whole buffer is
+    compared."""
+    curve, log_n, p = "bn254", 22, 0x2AAAAB
+    c = get_curve(curve)
+    n, r = 1 << log_n, c.r
+    assert n // ASVC_TILE == 2 * ASVC_THREADS and (n // 2) // ASVC_TILE <= ASVC_THREADS      # ntile: two windows here, one below
+    assert p % 2 == 1 and 0 < p < n                                  # w = root^p has full order
+    w = pow(ref.domain_of(curve, n).group_gen, p, r)
+    assert pow(w, n // 2, r) == r - 1 and pow(w, ASVC_TILE * ASVC_THREADS, r) == r - 1
+    rng = random.Random(22)
+    base = [rng.randrange(r) for _ in range(PERIOD)]
+    base[0], base[1] = 0, r - 1
+    base_words = codec.fr_to_mont(base, c)
+    base_m = codec.limbs_to_ints(base_words)                         # phi[t] R mod r
+    sent = np.full((1, 4), SENT, dtype=np.uint64)
+    host_in = np.concatenate([sent, base_words[np.arange(n) % PERIOD], sent])
+    acc, raw = 0, [b""] * (n - 1)
+    for t in range(n - 2, -1, -1):
+        acc = (base_m[(t + 1) % PERIOD] + w * acc) % r
+        raw[t] = acc.to_bytes(32, "little")
+    want = np.full((n + 1, 4), SENT, dtype=np.uint64)
+    want[1:-1] = np.frombuffer(b"".join(raw), dtype="<u8").reshape(n - 1, 4)
+    del raw
+    d_in, d_out = ctx.to_device(host_in), ctx.to_device(np.full((n + 1, 4), SENT, dtype=np.uint64))
+    try:
+        ctx.fr_asvc_quotient_dev(c, d_in + 32, log_n, [p], d_out + 32)
+        got_in, got = np.zeros_like(host_in), np.zeros_like(want)
+        ctx.d2h(got_in, d_in)
+        ctx.d2h(got, d_out)
+    finally:
+        ctx.dev_free(d_in)
+        ctx.dev_free(d_out)
+    assert np.array_equal(got_in, host_in), "the input changed"
+    assert np.array_equal(got, want)
 
 
 # ------------------------------------------------------------------------------------------- argument rules

@@ -1,7 +1,11 @@
 """zkp_gkr_layer_* / zkp_fr_gkr_eval_layer_dev / zkp_fr_gkr_tables_dev / zkp_fr_gkr_round_dev / ckb_zkp_amd.gkr on the device,
 bit-exact against tests/gkr_ref.py (Python integers that follow libra/src/circuit.rs, evaluate.rs, sumcheck.rs and
 libra_linear_gkr.rs).  Every output buffer starts as sentinels with one sentinel element before and after it, and whole buffers are
-compared."""
+compared.
+
+The second-stage loops take their second trip in test_tables_one_segment_of_more_chunks_than_threads (gkr_long_kernel: one node of
+GKR_THREADS GKR_CHUNK + 1 gates; 0.9 s a curve on an MI355X, the Python tables over 2^20 gates) and
+test_round_more_workgroups_than_final_threads (gkr_final_kernel: 2 GKR_THREADS workgroups; under 0.1 s a case)."""
 import ctypes
 
 import numpy as np
@@ -13,11 +17,14 @@ from ckb_zkp_amd.params import get_curve
 from tests import gkr_ref as ref
 from tests.gkr_cases import callbacks, load_mini, rand_fr, random_layers
 from tests.sumcheck_ref import combine_with_r
+from tests.util import csrc_constant, periodic_bind, periodic_round_sums
 
 pytestmark = pytest.mark.gpu
 CURVES = ["bn254", "bls12_381"]
 SENT = 0xABABABABABABABAB
 V = ctypes.c_void_p
+GKR_THREADS = csrc_constant("gkr.hip", "GKR_THREADS")      # threads of gkr_long_kernel and gkr_final_kernel: their loops' stride
+PERIOD = 1021                                               # long tables repeat a block of this (prime) length
 
 
 class Bufs:
@@ -197,6 +204,48 @@ def test_tables_two_long_nodes(ctx, curve):
 
 
 @pytest.mark.parametrize("curve", CURVES)
+def test_tables_one_segment_of_more_chunks_than_threads(ctx, curve):
+    """GKR_THREADS GKR_CHUNK + 1 gates, all of them (op, 0, 1): node 0 on the left and node 1 on the right each hold one segment of
+    GKR_THREADS + 1 chunks, so thread 0 of gkr_long_kernel adds a second partial (the chunk of one gate) in both phases.  G repeats
+    PERIOD values, the ops repeat a block of 7; the tables are eval_hg / eval_fgu over the whole gate list."""
+    c = get_curve(curve)
+    r = c.r
+    log_in, nodes = 1, 2
+    n_gates = GKR_THREADS * GKR_CHUNK + 1
+    assert -(-n_gates // GKR_CHUNK) == GKR_THREADS + 1 and n_gates > GKR_LONG
+    log_out = (n_gates - 1).bit_length()
+    op = np.resize(np.array([0, 1, 1, 0, 1, 0, 0], dtype=np.uint8), n_gates)
+    left, right = np.zeros(n_gates, dtype=np.uint32), np.ones(n_gates, dtype=np.uint32)
+    base = _values(c, PERIOD, 7)
+    idx = np.arange(1 << log_out) % PERIOD
+    g_vec, w_vec = [base[i] for i in idx.tolist()], [r - 1, rand_fr(r, 1, 8)[0]]
+    ref_gates = list(zip(range(n_gates), op.tolist(), left.tolist(), right.tolist()))
+    layer = ctx.gkr_layer_upload(op, left, right, log_in)
+    g_words = codec.fr_to_mont(base, c)[idx]
+    d_in = ctx.to_device(np.concatenate([g_words, codec.fr_to_mont(w_vec, c)]))
+    d_g, d_w = d_in, d_in + 32 * len(g_vec)
+    out = Bufs(ctx, 3, nodes)
+    try:
+        info = ctx.gkr_layer_info(layer)
+        assert (info["n_gates"], info["log_out"], info["log_in"], info["n_mul"]) == (n_gates, log_out, log_in, int(op.sum()))
+        assert (info["max_fan_left"], info["max_fan_right"], info["long_left"], info["long_right"]) == (n_gates, n_gates, 1, 1)
+        for phase in (1, 2):
+            exp = ref.eval_hg(g_vec, w_vec, ref_gates, log_in, r) if phase == 1 else ref.eval_fgu(g_vec, w_vec, ref_gates, log_in, r)
+            assert all(t[phase - 1] != 0 and t[2 - phase] == 0 for t in exp)      # the long node's slot; the other node has no gates
+            exp = list(exp) + [None] * (3 - len(exp))
+            out.fill(c, [None] * 3)
+            ctx.fr_gkr_tables_dev(c, layer, phase, d_g, d_w, out.ptrs()[:4 - phase])
+            assert np.array_equal(out.read(), out.expected(c, exp)), phase
+        got_in = np.zeros((len(g_vec) + 2, 4), dtype=np.uint64)
+        ctx.d2h(got_in, d_in)
+        assert np.array_equal(got_in[:-2], g_words), "G changed"
+    finally:
+        out.free()
+        ctx.dev_free(d_in)
+        ctx.gkr_layer_free(layer)
+
+
+@pytest.mark.parametrize("curve", CURVES)
 def test_tables_errors_leave_everything_untouched(ctx, curve):
     c = get_curve(curve)
     log_in, nodes = 4, 16
@@ -294,6 +343,43 @@ def test_round(ctx, curve, phase, length):
             bufs.fill(c, tables)
             ctx.fr_gkr_round_dev(c, phase, bufs.ptrs(), length, fu=m(fus[-1]), bind=m(edge), want_evals=False)
             assert np.array_equal(bufs.read(), bufs.expected(c, [combine_with_r(t, edge, r) + t[half:] for t in tables])), edge
+    finally:
+        bufs.free()
+
+
+@pytest.mark.parametrize("bind", [False, True])
+@pytest.mark.parametrize("phase", [1, 2])
+@pytest.mark.parametrize("curve", CURVES)
+def test_round_more_workgroups_than_final_threads(ctx, curve, phase, bind):
+    """2^18 elements without a bind, 2^19 with one: h = 2^17 columns, 2 GKR_THREADS workgroups, the shortest tables at which every
+    thread of gkr_final_kernel adds a second partial.  The tables repeat PERIOD values each, so the sums are formed per residue
+    (tests/util.periodic_round_sums over ref.round_evals) and the bound halves repeat periodic_bind's block."""
+    c = get_curve(curve)
+    r = c.r
+    nt = 5 - phase
+    length = 1 << (19 if bind else 18)
+    h = length // (4 if bind else 2)
+    assert GKR_THREADS < h // GKR_THREADS <= 2 * GKR_THREADS and (h // 2) // GKR_THREADS <= GKR_THREADS
+    bases = [_values(c, PERIOD, 1000 * phase + 10 * bind + i) for i in range(nt)]
+    fu = None if phase == 1 else rand_fr(r, 1, 91)[0]
+    assert fu not in (0, 1)
+    x = rand_fr(r, 1, 92)[0]
+    m = lambda v: None if v is None else codec.fr_mont(v, c)      # noqa: E731
+    idx = np.arange(length) % PERIOD
+    evals = lambda t: ref.round_evals(phase, t, fu, r)            # noqa: E731
+    bufs = Bufs(ctx, nt, length)
+    try:
+        for i, b in enumerate(bases):
+            bufs.host[i, 1:-1] = codec.fr_to_mont(b, c)[idx]
+        ctx.h2d(bufs.dev, bufs.host)
+        exp = bufs.host.copy()
+        if bind:
+            bases = [periodic_bind(b, length // 2, x, r) for b in bases]
+            for i, b in enumerate(bases):
+                exp[i, 1:1 + length // 2] = codec.fr_to_mont(b, c)[idx[:length // 2]]       # the upper half untouched
+        got = ctx.fr_gkr_round_dev(c, phase, bufs.ptrs(), length, fu=m(fu), bind=m(x) if bind else None)
+        assert tuple(codec.fr_from_mont(got, c)) == periodic_round_sums(evals, bases, h, r)
+        assert np.array_equal(bufs.read(), exp)
     finally:
         bufs.free()
 

@@ -1,6 +1,8 @@
 """zkp_fr_gkr_eval_layer_batch_dev / zkp_fr_gkr_dp_round_dev / ckb_zkp_amd.hyrax on the device, bit-exact against tests/hyrax_ref.py
 (Python integers that follow hyrax/src/zk_sumcheck_proof.rs, hyrax_proof.rs, evaluate.rs and circuit.rs).  Every buffer the device
-may write starts with one sentinel element before and after it, whole buffers are compared and the inputs are read again."""
+may write starts with one sentinel element before and after it, whole buffers are compared and the inputs are read again.
+test_rounds_more_workgroups_than_sum_threads (HYRAX_THREADS + 1 workgroups under fr_sum_partials) takes under 0.1 s a case on an
+MI355X."""
 import ctypes
 
 import numpy as np
@@ -140,6 +142,18 @@ def test_rounds_gate_kinds(ctx, curve, kind):
 def test_rounds_chunk_boundaries(ctx, curve, n_gates):
     gates = random_layers([n_gates], 32, n_gates)[0]
     _check_sequence(ctx, get_curve(curve), gates, 5, 4, n_gates)
+
+
+# HYRAX_THREADS chunks and one more over one workgroup of columns: gx = 1, gy = HYRAX_THREADS + 1 workgroups leave their partials, the
+# fewest at which a thread of fr_sum_partials adds a second one; a chunk finds its node by binary search among about a thousand
+# entries per node.  n = 2: round 0 (no bind) and the closing call; n = 4: also one bind-and-evaluate round over 257 workgroups
+@pytest.mark.parametrize("n", [2, 4])
+@pytest.mark.parametrize("curve", CURVES)
+def test_rounds_more_workgroups_than_sum_threads(ctx, curve, n):
+    n_gates = HYRAX_THREADS * HYRAX_CHUNK + 1
+    assert -(-n_gates // HYRAX_CHUNK) == HYRAX_THREADS + 1 and n // 2 <= HYRAX_THREADS
+    gates = random_layers([n_gates], 8, n_gates)[0]
+    _check_sequence(ctx, get_curve(curve), gates, 3, n, n_gates + n)
 
 
 @pytest.mark.parametrize("curve", CURVES)

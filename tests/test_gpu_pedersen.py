@@ -5,7 +5,11 @@ multiplication, (sum_j s_j a_j + blind a_h) G, whatever cols is; the outputs are
 Equal generators (a_1 = a_0), opposite ones (a_1 = r - a_0), identities (a_j = 0) and h = g_0 are such keys too.  Every writable
 buffer starts as sentinels with one sentinel element before and after it, whole buffers are compared, and the inputs are read back
 unchanged.  G (generators per slice) and c come from zkp_pedersen_key_info, so the shapes follow the plan: one slice, one slice
-exactly, two and three slices; 63 / 64 / 65 rows are the batch of the affine pass."""
+exactly, two and three slices; 63 / 64 / 65 rows are the batch of the affine pass.
+
+Rows of more slices than the row pass has lanes (test_row_pass_second_trip: 64, 65 and 66 slices) and the key cap (test_key_cap:
+65536 generators, 529 slices) use keys that repeat PERIOD of the base points.  Measured on an MI355X: a case of
+test_row_pass_second_trip takes 0.04 - 0.2 s (its two keys 0.4 s once), test_key_cap 0.14 s."""
 import functools
 import random
 
@@ -14,6 +18,7 @@ import pytest
 
 from ckb_zkp_amd import _lib, codec
 from ckb_zkp_amd.params import get_curve
+from ckb_zkp_amd.polycommit import PEDERSEN_MAX_GENS, PEDERSEN_ROW_LANES
 from oracle.pyref.curves import Group
 from tests.util import OC
 
@@ -24,6 +29,9 @@ ROWS = [1, 2, 63, 64, 65]
 MAX_GENS, MAX_CELLS = 65536, 1 << 28
 G_PLAN, C_PLAN = 124, 8                  # what zkp_pedersen_key_info reports (asserted below): sizes the shared key before a context exists
 NG = 2 * G_PLAN + 2                      # generators of the shared key: every cols below is < n_gens
+LANES = PEDERSEN_ROW_LANES               # lane t of the row pass adds slices t, t + LANES, ... of its row
+LONG_COLS = [LANES * G_PLAN, LANES * G_PLAN + 1, (LANES + 1) * G_PLAN + 1]       # one slice per lane; lane 0, lanes 0 and 1 take a second
+PERIOD = 64                              # of the long keys' generators: no multiple or divisor of G_PLAN, LANES g is a multiple of it
 
 
 def _bad(fn, status=-1):
@@ -174,6 +182,81 @@ def test_scalar_patterns(keys, curve):
     assert (inf == 1).all() and (xy == 0).all()
     one_xy, one_inf = key.ctx.fixed_base_mul(key.c, 1, codec.g1_to_mont([point_of(curve, 1)], key.c)[0][0], codec.fr_canonical([0], key.c))
     assert np.array_equal(one_xy[0], xy[0]) and one_inf[0] == inf[0]
+
+
+# ------------------------------------------------------------------------------------------- rows of more slices than lanes
+def periodic_exps(curve, n):
+    """n generator exponents that repeat the first PERIOD known-dlog base points: no new point_of call, whatever n is"""
+    e = base_exps(curve)
+    return [e[j % PERIOD] for j in range(n)]
+
+
+@pytest.fixture(scope="module")
+def long_keys(ctx):
+    made = {}
+
+    def get(curve):
+        if curve not in made:
+            made[curve] = Key(ctx, curve, periodic_exps(curve, LONG_COLS[-1]), base_exps(curve)[NG])
+        return made[curve]
+    yield get
+    for k in made.values():
+        k.free()
+
+
+def row_plan(key, cols):
+    """(S, g) of pedersen_plan from the G the key reports"""
+    G = key.info["gens_per_slice"]
+    S = -(-cols // G)
+    return S, -(-cols // S)
+
+
+@pytest.mark.parametrize("cols", LONG_COLS)
+@pytest.mark.parametrize("curve", CURVES)
+def test_row_pass_second_trip(long_keys, curve, cols):
+    """ped_row_kernel's lane t adds slices t, t + LANES, ...: LANES G columns are the last shape of one slice per lane, one column
+    more gives lane 0 a second slice (the plan balances the slices, so S = LANES + 1 slices of g < G generators, the last one
+    shorter), (LANES + 1) G + 1 columns give lanes 0 and 1 one.  The key repeats PERIOD base points (periodic_exps), so the reference
+    of a row stays one scalar multiplication.  A slice holds more than PERIOD generators, so points repeat inside it and enter one
+    bucket twice whenever their digits agree: always in the row whose scalars are all equal, where the bucket sums meet additions of
+    equal points.  That is kept on purpose.  In that row at (LANES + 1) G + 1 columns slices 0 and LANES hold the same generators
+    (LANES g is a multiple of PERIOD) and return the same point, so lane 0's second addition is a doubling."""
+    key = long_keys(curve)
+    G, r = key.info["gens_per_slice"], key.c.r
+    assert G == G_PLAN and G % PERIOD and PERIOD % G and key.info["n_gens"] == LONG_COLS[-1] >= cols
+    S, g = row_plan(key, cols)
+    assert S == {LANES * G: LANES, LANES * G + 1: LANES + 1, (LANES + 1) * G + 1: LANES + 2}[cols]
+    assert (S > LANES) == (cols > LANES * G) and (S - 1) * g < cols <= S * g <= S * G and g > PERIOD
+    if cols == LONG_COLS[-1]:                                       # slice LANES is a whole slice over the generators of slice 0
+        assert (LANES * g) % PERIOD == 0 and (LANES + 1) * g <= cols
+    rng = random.Random(f"long {curve} {cols}")
+    equal = [rng.randrange(1, r)] * cols
+    one = [[rng.randrange(r) for _ in range(cols)]]
+    check(key, one, [rng.randrange(r)], (curve, 1, cols, "blind"))
+    check(key, one, None, (curve, 1, cols, "no blind"))
+    two = [[rng.randrange(r) for _ in range(cols)], equal]
+    check(key, two, [rng.randrange(r), rng.randrange(r)], (curve, 2, cols, "blinds"))
+    check(key, two, None, (curve, 2, cols, "no blinds"))
+    check(key, [equal], None, (curve, 1, cols, "all equal"))
+
+
+def test_key_cap(ctx):
+    """n_gens = cols = PED_MAX_GENS on BN254: S = 529 slices, eight or nine per lane of the row pass, and 1025 workgroups per level
+    of key creation; one row with a blind.  The table (about 138 MB) is freed whatever happens."""
+    curve = "bn254"
+    c = get_curve(curve)
+    key = Key(ctx, curve, periodic_exps(curve, MAX_GENS), base_exps(curve)[NG])
+    try:
+        info = key.info
+        assert info["n_gens"] == MAX_GENS == PEDERSEN_MAX_GENS and info["gens_per_slice"] == G_PLAN and info["launches"] == 3
+        assert info["table_bytes"] == info["W"] * (MAX_GENS + 1) * 2 * c.fq_limbs * 8
+        S, g = row_plan(key, MAX_GENS)
+        assert S > 8 * LANES and (S - 1) * g < MAX_GENS <= S * g <= S * G_PLAN
+        assert -(-(MAX_GENS + 1) // LANES) == MAX_GENS // LANES + 1 > 1024       # workgroups of a level of key creation
+        rng = random.Random("cap")
+        check(key, [[rng.randrange(c.r) for _ in range(MAX_GENS)]], [rng.randrange(1, c.r)], (curve, "cap"))
+    finally:
+        key.free()
 
 
 @pytest.mark.parametrize("variant", ["equal", "opposite", "flagged_identity", "zero_words_identity", "h_is_g0", "h_identity"])

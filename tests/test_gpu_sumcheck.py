@@ -1,7 +1,10 @@
 """zkp_fr_sumcheck_round_dev / zkp_fr_eq_evals_dev / ckb_zkp_amd.sumcheck on the device, bit-exact against tests/sumcheck_ref.py
-(Python integers that follow spartan/src/polynomial.rs and prover.rs) and, at full size, against oracle/cpu's fr_dot."""
+(Python integers that follow spartan/src/polynomial.rs and prover.rs) and, at full size, against oracle/cpu's fr_dot.
+test_round_more_workgroups_than_sum_threads (2 SC_THREADS workgroups under fr_sum_partials, one round checked on its own, also
+with ZKP_TEST_FULL=0) takes about 0.1 s a case on an MI355X."""
 import ctypes
 import hashlib
+import random
 
 import numpy as np
 import pytest
@@ -10,12 +13,14 @@ from ckb_zkp_amd import api, codec, sumcheck
 from ckb_zkp_amd.params import get_curve
 from oracle import cpu_oracle
 from tests import sumcheck_ref as ref
-from tests.util import TEST_FULL
+from tests.util import TEST_FULL, csrc_constant, periodic_bind, periodic_round_sums
 
 pytestmark = pytest.mark.gpu
 CURVES = ["bn254", "bls12_381"]
 KINDS = [api.SC_EQ_AB_MINUS_C, api.SC_PROD2, api.SC_PROD3]
 SENT = 0xABABABABABABABAB
+SC_THREADS = csrc_constant("sumcheck.hip", "SC_THREADS")         # threads of sc_round_kernel and of its fr_sum_partials
+PERIOD = 1021                                                      # long tables repeat a block of this (prime) length
 STEP = 37                                                          # table i of a case is pool[STEP i : STEP i + len]
 
 
@@ -162,6 +167,46 @@ def test_shared_tables(ctx, curve):
         assert np.array_equal(got[2:5, :n // 2], b_words[2:5]) and np.array_equal(got[2:5, n // 2:], t.words[2:5, n // 2:])
     finally:
         t.free()
+
+
+@pytest.mark.parametrize("bind", [False, True])
+@pytest.mark.parametrize("curve", CURVES)
+def test_round_more_workgroups_than_sum_threads(ctx, curve, bind):
+    """2^18 elements without a bind, 2^19 with one: h = 2^17 columns in 2 SC_THREADS workgroups, the fewest at which a thread of
+    fr_sum_partials adds a second partial of sc_round_kernel's layout (out NP + p) gridDim.x + blockIdx.x.  Two SC_EQ_AB_MINUS_C
+    terms share their eq table, so they run in one group and the second term's partials lie behind the first's.  The tables repeat
+    PERIOD values each: the sums are formed per residue (tests/util.periodic_round_sums over ref.round_evals), the bound halves
+    repeat periodic_bind's block.  One sentinel element before the first and after the last table."""
+    c = get_curve(curve)
+    r, kind = c.r, api.SC_EQ_AB_MINUS_C
+    n = 1 << (19 if bind else 18)
+    h = n // (4 if bind else 2)
+    assert SC_THREADS < h // SC_THREADS <= 2 * SC_THREADS and (h // 2) // SC_THREADS <= SC_THREADS
+    terms = [(0, 1, 2, 3), (0, 4, 5, 6)]
+    rng = random.Random(f"{curve} {bind}")
+    bases = [[rng.randrange(r) for _ in range(PERIOD)] for _ in range(7)]
+    for b in bases:
+        b[3], b[5] = 0, r - 1
+    x = rng.randrange(2, r)
+    idx = np.arange(n) % PERIOD
+    sent = np.full((1, 4), SENT, dtype=np.uint64)
+    host = np.concatenate([sent] + [codec.fr_to_mont(b, c)[idx] for b in bases] + [sent])
+    dev = ctx.to_device(host)
+    try:
+        ptrs = [dev + 32 * (1 + n * i) for term in terms for i in term]
+        exp = host.copy()
+        if bind:
+            bases = [periodic_bind(b, n // 2, x, r) for b in bases]
+            for i, b in enumerate(bases):
+                exp[1 + n * i:1 + n * i + n // 2] = codec.fr_to_mont(b, c)[idx[:n // 2]]     # the upper half untouched
+        ev = ctx.fr_sumcheck_round_dev(c, kind, ptrs, n, bind=_m(c, x) if bind else None)
+        want = [periodic_round_sums(lambda t: ref.round_evals(kind, t, r), [bases[i] for i in term], h, r) for term in terms]
+        assert _ints(c, ev) == want
+        got = np.zeros_like(host)
+        ctx.d2h(got, dev)
+        assert np.array_equal(got, exp)
+    finally:
+        ctx.dev_free(dev)
 
 
 # ------------------------------------------------------------------------------------------- argument rules

@@ -9,6 +9,8 @@ from pathlib import Path
 
 import pytest
 
+from ckb_zkp_amd import polycommit
+
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "ckb_zkp_amd" / "csrc"
 SRC = ROOT / "tests" / "c" / "pedersen_plan.cpp"
@@ -64,6 +66,24 @@ def test_plan_matches_the_model_and_keeps_its_bounds(prog, curve):
                 seen[k] += 1
         assert seen == [1] * n_gens, (curve, n_gens)
         assert p["max_gens"] == 65536 and n_gens <= p["max_gens"]
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_rows_of_more_slices_than_the_row_pass_has_lanes(prog, curve):
+    """cols at which a lane of the row pass (ped_row_kernel: slices t, t + lanes, ...) takes a second slice, and the key cap, where
+    a lane takes nine: the last row of one slice per lane, one generator more (the plan balances: S = lanes + 1 slices of g < G),
+    one slice more, PED_MAX_GENS.  tests/test_gpu_pedersen.py runs these shapes on the device."""
+    one = plan_of(prog, curve, 1)
+    G, lanes, cap = one["G"], one["lanes"], one["max_gens"]
+    assert lanes == polycommit.PEDERSEN_ROW_LANES
+    want_s = {lanes * G: lanes, lanes * G + 1: lanes + 1, (lanes + 1) * G + 1: lanes + 2, cap: -(-cap // G)}
+    assert max(want_s) == cap and want_s[cap] > 8 * lanes
+    for cols, S in want_s.items():
+        p = plan_of(prog, curve, cols)
+        assert p == model(curve, cols), (curve, cols)
+        assert p["S"] == S and (p["S"] > lanes) == (cols > lanes * G), (curve, cols)
+        assert (p["S"] - 1) * p["g"] < cols <= p["S"] * p["g"] <= p["S"] * p["G"], (curve, cols)
+        assert p["g"] * p["W"] <= p["max_entries"] and p["lds_bytes"] <= p["lds_max"], (curve, cols)
 
 
 def test_every_column_count_near_the_slice_boundaries_is_covered(prog):

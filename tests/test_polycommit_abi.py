@@ -43,6 +43,7 @@ def test_constants_agree():
     assert define("ZKP_FR_VECMAT_ROW_CHUNK") == polycommit.VECMAT_ROW_CHUNK
     assert f"constexpr uint32_t PED_MAX_GENS = {polycommit.PEDERSEN_MAX_GENS};" in hpp
     assert f"constexpr uint32_t VECMAT_ROW_CHUNK = {polycommit.VECMAT_ROW_CHUNK};" in hpp
+    assert f"constexpr int PED_LANES = {polycommit.PEDERSEN_ROW_LANES};" in hpp
     assert "constexpr uint64_t PED_MAX_CELLS = (uint64_t)1 << 28;" in hpp and polycommit.MAX_CELLS == 1 << 28
     assert "rows * cols <= 2^28" in text
     assert polycommit.split_sizes(20) == (1 << 10, 1 << 10) and polycommit.split_sizes(5) == (4, 8) and polycommit.split_sizes(0) == (1, 1)

@@ -43,6 +43,36 @@ def variant_ctx(monkeypatch, device, config, env):
         v.close()
 
 
+def csrc_constant(file, name):
+    """the value of `constexpr <integer type> name = <decimal>;` in ckb_zkp_amd/csrc/<file>: the sizes a unit keeps to itself"""
+    import re
+    from pathlib import Path
+    text = (Path(__file__).resolve().parent.parent / "ckb_zkp_amd" / "csrc" / file).read_text()
+    found = re.findall(rf"constexpr (?:int|uint32_t|size_t) {name} = (\d+);", text)
+    assert len(found) == 1, (file, name, found)
+    return int(found[0])
+
+
+# Long tables for the round kernels repeat a block of prime length: t[j] = base[j % P].  A round pairs t[j] with t[j + h] for
+# j < h, so the term of index j depends on j % P alone and the sum over j < h is formed per residue, with Python integers, from
+# P (not h) terms.
+def periodic_round_sums(evals, bases, h, r):
+    """the sums over j < h of a round whose tables are t_s[j] = bases[s][j % P].  evals(tables) -> a tuple of sums over the pairs
+    (tables[s][i], tables[s][i + len / 2]): the reference's own round function.  floor(h / P) whole periods plus the first h % P
+    residues once more."""
+    P = len(bases[0])
+    assert all(len(b) == P for b in bases)
+    q, rem = divmod(h, P)
+    cut = lambda k: [[b[c] for c in range(k)] + [b[(c + h) % P] for c in range(k)] for b in bases]   # noqa: E731
+    return tuple((q * a + b) % r for a, b in zip(evals(cut(P)), evals(cut(rem))))
+
+
+def periodic_bind(base, m, x, r):
+    """the block that t[j] + x (t[j + m] - t[j]), j < m, repeats when t[j] = base[j % P]"""
+    P = len(base)
+    return [(base[c] + x * (base[(c + m) % P] - base[c])) % r for c in range(P)]
+
+
 def jac_to_affine(ctx, curve, group, xyz):
     """device Jacobian limbs -> oracle-style affine point via zkp_g*_into_affine."""
     c = get_curve(curve)
