@@ -12,6 +12,7 @@ from ckb_zkp_amd import codec, groth16, serialize
 from ckb_zkp_amd.circuits import mimc_chain_instance
 from ckb_zkp_amd.params import get_curve
 from oracle.pyref import serialize as oser
+from tests.codec_cases import curve_point_outside_subgroup as _curve_point_outside_subgroup
 from tests.util import OC
 
 TOXIC = dict(alpha=0x1234567890ABCDEF1, beta=0xFEDCBA09876543211, gamma=0x1111111111111111111, delta=0x2222222222222222223, tau=0x3333333333333333335)
@@ -141,24 +142,6 @@ def test_parameters_bytes_roundtrip_proves_the_same(ctx, curve):
 
 
 # ------------------------------------------------------------------------------------------- checked deserialize (subgroup)
-def _curve_point_outside_subgroup(curve, group):
-    """a point ON the curve whose order does not divide r (cofactor groups only): decompress small x values until one works"""
-    from oracle.pyref.curves import Group
-    c = get_curve(curve)
-    n = 8 * c.fq_limbs
-    G = Group(OC[curve], group)
-    x = 1
-    while True:
-        data = x.to_bytes(n, "little") + (b"" if group == 1 else (1).to_bytes(n, "little"))
-        x += 1
-        try:
-            P = oser.point_decode(data, OC[curve], group, checked=False)
-        except oser.InvalidData:
-            continue
-        if P is not None and G.on_curve(P) and not oser.in_subgroup(P, OC[curve], group):
-            return P
-
-
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
 @pytest.mark.parametrize("group", [1, 2])
 def test_subgroup_check_accepts_subgroup_points_and_rejects_off_curve(ctx, curve, group):
