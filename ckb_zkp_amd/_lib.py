@@ -180,6 +180,8 @@ SIGNATURES = {
     "zkp_pedersen_key_info": (C.c_int32, [vp, u64p]),
     "zkp_pedersen_commit_rows_dev": (C.c_int32, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]),
     "zkp_fr_vecmat_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp]),
+    "zkp_g1_scale_vec_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]),
+    "zkp_g1_ntt_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, C.c_int32]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

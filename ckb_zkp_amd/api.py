@@ -234,6 +234,52 @@ class Context:
             for p in bufs:
                 self.dev_free(p)
 
+    def g1_scale_vec_dev(self, curve, xy_dev: int, inf_dev, scalars_dev: int, n: int, out_xy_dev: int, out_inf_dev: int):
+        """zkp_g1_scale_vec_dev: out[i] = [s_i] P_i over DEVICE pointers (G1; flags None / 0 = none; scalars Montgomery Fr; out may
+        equal the input).  Launches only."""
+        _lib.check(self.lib.zkp_g1_scale_vec_dev(self.h, get_curve(curve).cid, C.c_void_p(xy_dev or 0), C.c_void_p(inf_dev or 0),
+                                                 C.c_void_p(scalars_dev or 0), n, C.c_void_p(out_xy_dev or 0),
+                                                 C.c_void_p(out_inf_dev or 0)), "zkp_g1_scale_vec_dev")
+
+    def g1_ntt_dev(self, curve, xy_dev: int, inf_dev: int, log_n: int, op: int):
+        """zkp_g1_ntt_dev: the transform over 2^log_n G1 points in place over DEVICE pointers (op NTT_FFT / NTT_IFFT, the root of
+        ntt_dev; flags required).  Launches only."""
+        _lib.check(self.lib.zkp_g1_ntt_dev(self.h, get_curve(curve).cid, C.c_void_p(xy_dev or 0), C.c_void_p(inf_dev or 0), log_n, op),
+                   "zkp_g1_ntt_dev")
+
+    def _g1_points_run(self, xy: np.ndarray, inf, extra, run):
+        """upload (n, w) points, (n,) flags (None = none) and the arrays of `extra`, call run(d_xy, d_inf, *d_extra), download"""
+        xy = _c64(xy)
+        n = xy.shape[0]
+        flags = np.zeros(n, dtype=np.uint8) if inf is None else np.ascontiguousarray(inf, dtype=np.uint8)[:n].copy()
+        out = xy.copy()
+        bufs = []
+        try:
+            for a in [out, flags] + [np.ascontiguousarray(e) for e in extra]:
+                bufs.append(self.to_device(a))
+            run(*bufs)
+            self.d2h(out, bufs[0])
+            self.d2h(flags, bufs[1])
+            return out, flags
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+
+    def g1_scale_vec(self, curve, xy: np.ndarray, inf, scalars_mont: np.ndarray):
+        """Host convenience over g1_scale_vec_dev: ((n, w) affine Montgomery, (n,) identity flags) of [s_i] P_i."""
+        s = _c64(scalars_mont)
+        n = _c64(xy).shape[0]
+        assert s.shape == (n, 4)
+        if n == 0:
+            return _c64(xy).copy(), np.zeros(0, dtype=np.uint8)
+        return self._g1_points_run(xy, inf, [s], lambda d, di, ds: self.g1_scale_vec_dev(curve, d, di, ds, n, d, di))
+
+    def g1_ntt(self, curve, xy: np.ndarray, inf, op: int):
+        """Host convenience over g1_ntt_dev: the transformed copy of (2^k, w) points and their identity flags."""
+        n = _c64(xy).shape[0]
+        assert n >= 2 and n & (n - 1) == 0
+        return self._g1_points_run(xy, inf, [], lambda d, di: self.g1_ntt_dev(curve, d, di, n.bit_length() - 1, op))
+
     def fr_dot_batch_dev(self, curve, a_ptrs, b_ptrs, ns) -> np.ndarray:
         """zkp_fr_dot_batch_dev: <a_k, b_k> over DEVICE Fr vectors (Montgomery) -> (count, 4) uint64 Montgomery."""
         k = len(ns)

@@ -8,6 +8,9 @@ update_commit_many / update_proof_many.
   * commit: the values go to the device once, then zkp_msm_g1_mont_dev over the resident l_of_g1;
   * prove_pos: zkp_ntt_dev (inverse), zkp_fr_asvc_quotient_dev, zkp_msm_g1_mont_dev over the resident powers_of_g1;
   * aggregate_proofs: zkp_fr_asvc_subset_weights_dev, then one variable-base MSM;
+  * all_proofs_key / prove_all: all n single-position proofs from three zkp_g1_ntt_dev transforms (one of them once per key), one
+    zkp_g1_scale_vec_dev and two zkp_ntt_dev transforms (Tomescu et al. §3.4, after Feist-Khovratovich); lagrange_from_powers:
+    l_of_g1 from the powers of tau with one inverse zkp_g1_ntt_dev, without the trapdoor;
   * the updates: their few scalars are host integers, the point work one variable-base MSM; the *_many forms prepare their m scalars
     on the device (powers of w gathered at the changed positions, element-wise products, one batch inversion) and run one
     zkp_msm_g1_var_batch_dev call.
@@ -21,7 +24,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .api import NTT_IFFT, VEC_ADDC, VEC_MUL, VEC_SCALE
+from .api import NTT_FFT, NTT_IFFT, VEC_ADDC, VEC_MUL, VEC_SCALE
 from .codec import fr_mont, fr_to_mont
 from .params import get_curve
 
@@ -33,6 +36,8 @@ ASVC_CHUNK = 32                # segment heads per thread of the scan
 ASVC_TILE = ASVC_CHUNK * ASVC_THREADS
 ASVC_MAX_LOG = 30
 MSM_SMALL_MAX_G1 = 1 << 16     # ZKP_MSM_SMALL_MAX_G1: the *_many forms run one batched small MSM
+G1_NTT_MAX_LOG = 24            # ZKP_G1_NTT_MAX_LOG
+G1_NTT_LANES = 64              # csrc/g1_ntt.hpp: one wave per workgroup
 
 
 def segment_length(k: int) -> int:
@@ -205,6 +210,112 @@ def prove_pos(pk: ProvingKey, values, points, stats: dict | None = None):
         ctx.sync()
         ctx.dev_free(d_phi)
         ctx.dev_free(d_q)
+
+
+@dataclass
+class AllProofsKey:
+    """the resident table A of prove_all: the size-2n transform of (tau^(n-2), ..., tau, 1, 0, ..., 0) g1 as device points"""
+    curve: object
+    n: int
+    ctx: object
+    a_xy: int = 0
+    a_inf: int = 0
+
+    def free(self):
+        for p in (self.a_xy, self.a_inf):
+            if p:
+                self.ctx.dev_free(p)
+        self.a_xy = self.a_inf = 0
+
+
+def _g1_log(c, size: int) -> int:
+    log = size.bit_length() - 1
+    if size != 1 << log or log < 1 or log > min(G1_NTT_MAX_LOG, c.two_adicity):
+        raise ValueError(f"a G1 transform takes 2^1 .. 2^{min(G1_NTT_MAX_LOG, c.two_adicity)} points")
+    return log
+
+
+def all_proofs_key(ctx, pk: ProvingKey) -> AllProofsKey:
+    """the key of prove_all: a_k = powers_of_g1[n-2-k] for k <= n-2 and the identity up to 2n, transformed once (size 2n)"""
+    c, n = pk.curve, pk.n
+    log2n = _g1_log(c, 2 * n)
+    a = np.zeros((2 * n, 2 * c.fq_limbs), dtype=np.uint64)
+    a[:n - 1] = np.asarray(pk.powers_of_g1, dtype=np.uint64)[n - 2::-1]
+    flags = np.ones(2 * n, dtype=np.uint8)
+    flags[:n - 1] = 0
+    apk = AllProofsKey(c, n, ctx)
+    try:
+        apk.a_xy, apk.a_inf = ctx.to_device(a), ctx.to_device(flags)
+        ctx.g1_ntt_dev(c, apk.a_xy, apk.a_inf, log2n, NTT_FFT)
+        ctx.sync()
+    except Exception:
+        apk.free()
+        raise
+    return apk
+
+
+def prove_all(pk: ProvingKey, apk: AllProofsKey, values, stats: dict | None = None):
+    """every single-position proof at once: ((n, w) affine Montgomery, (n,) identity flags), proof i equal to
+    prove_pos(pk, values, [i]) bit for bit.  With c the coefficients of the values' polynomial,
+    q_i(tau) = sum_m w^(i m) h_m(tau) and h_m = sum_{j <= n-2-m} c_{m+1+j} tau^j = (a * b)_{n-1+m} for a = (tau^(n-2), ..., 1) and
+    b = c, a linear convolution that the cyclic one of size 2n holds (degree <= 2n - 3): B = FFT_2n(c, 0 x n), conv =
+    IFFT_2n(A_i B_i), proofs = FFT_n(conv[n-1 .. 2n-2]) (conv[2n-2] is the identity h_{n-1}).  stats (a dict) receives the host's
+    wall seconds per stage."""
+    ctx, c, n = apk.ctx, pk.curve, pk.n
+    if apk.n != n or get_curve(apk.curve) is not get_curve(c) or not apk.a_xy:
+        raise ValueError("the all-proofs key belongs to another proving key")
+    if not 1 <= len(values) <= n:
+        raise ValueError("between 1 and n values")
+    log_n, log2n = n.bit_length() - 1, _g1_log(c, 2 * n)
+    pb = 16 * c.fq_limbs                                                # bytes of one affine point
+    clock = [time.perf_counter()]
+
+    def lap(key):
+        ctx.sync()
+        now = time.perf_counter()
+        if stats is not None:
+            stats[key] = stats.get(key, 0.0) + now - clock[0]
+        clock[0] = now
+
+    padded = np.zeros((2 * n, 4), dtype=np.uint64)
+    padded[:len(values)] = fr_to_mont(values, c)
+    bufs = []
+    try:
+        bufs.append(ctx.to_device(padded))
+        bufs.append(ctx.dev_alloc(2 * n * pb))
+        bufs.append(ctx.dev_alloc(2 * n))
+        d_b, d_xy, d_inf = bufs
+        lap("upload")
+        ctx.ntt_dev(c, d_b, log_n, NTT_IFFT)                            # c_0 .. c_{n-1}; the upper half stays zero
+        lap("ifft")
+        ctx.ntt_dev(c, d_b, log2n, NTT_FFT)                             # B
+        lap("fft")
+        ctx.g1_scale_vec_dev(c, apk.a_xy, apk.a_inf, d_b, 2 * n, d_xy, d_inf)
+        lap("scale")
+        ctx.g1_ntt_dev(c, d_xy, d_inf, log2n, NTT_IFFT)                 # conv
+        lap("g1_ifft")
+        ctx.g1_ntt_dev(c, d_xy + (n - 1) * pb, d_inf + n - 1, log_n, NTT_FFT)   # H -> the proofs, in place
+        lap("g1_fft")
+        out, inf = np.zeros((n, 2 * c.fq_limbs), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        ctx.d2h(out, d_xy + (n - 1) * pb)
+        ctx.d2h(inf, d_inf + n - 1)
+        lap("download")
+        return out, inf
+    finally:
+        ctx.sync()
+        for p in bufs:
+            ctx.dev_free(p)
+
+
+def lagrange_from_powers(ctx, curve, powers_xy, n: int):
+    """l_of_g1 from powers_of_g1[:n] without the trapdoor: L_i(tau) = (1/n) sum_j w^(-i j) tau^j is one inverse transform over G1.
+    Returns ((n, w) affine Montgomery, (n,) identity flags)."""
+    c = get_curve(curve)
+    _g1_log(c, n)
+    xy = np.ascontiguousarray(powers_xy, dtype=np.uint64)
+    if xy.ndim != 2 or xy.shape[0] < n:
+        raise ValueError("n powers of tau are needed")
+    return ctx.g1_ntt(c, xy[:n], None, NTT_IFFT)
 
 
 def _msm_points(ctx, c, points, scalars):

@@ -13,6 +13,7 @@
 #include "internal.hpp"
 #include "ipa.hpp"
 #include "fr_open.hpp"
+#include "g1_ntt.hpp"
 #include "pedersen.hpp"
 #include "plonk.hpp"
 #include "spark.hpp"
@@ -922,6 +923,15 @@ int32_t zkp_fr_vecmat_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_dev
                           uint64_t* out_dev) {
   if (!l_dev || !m_dev || !out_dev) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { pedersen_vtbl(curve)->vecmat(ctx, l_dev, m_dev, rows, cols, out_dev); });
+}
+int32_t zkp_g1_scale_vec_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy_dev, const uint8_t* inf_dev, const uint64_t* scalars_dev,
+                             size_t n, uint64_t* out_xy_dev, uint8_t* out_inf_dev) {
+  if (n && (!xy_dev || !scalars_dev || !out_xy_dev || !out_inf_dev)) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { g1_ntt_vtbl(curve)->scale_vec(ctx, xy_dev, inf_dev, scalars_dev, n, out_xy_dev, out_inf_dev); });
+}
+int32_t zkp_g1_ntt_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* xy_dev, uint8_t* inf_dev, uint32_t log_n, int32_t op) {
+  if (!xy_dev || !inf_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { g1_ntt_vtbl(curve)->ntt(ctx, xy_dev, inf_dev, log_n, op); });
 }
 int32_t zkp_bench_mulmod(zkp_ctx* ctx, zkp_curve_t curve, int32_t field, int32_t unsaturated, double* out) {
   if (!out || (curve != ZKP_BN254 && curve != ZKP_BLS12_381) || field < 0 || field > 1) return ZKP_ERR_BAD_ARG;

@@ -167,6 +167,7 @@ struct zkp_ctx {
   bool batch_mode = false;     // inside zkp_groth16_prove_batch*: kernels are tuned for throughput of many proofs in flight, not latency
   std::map<std::pair<int, int>, zkp::NttTables> ntt_tables;   // (curve, log_n)
   zkp::DevBuf ntt_io, poly_tmp, poly_consts, spmv_list;
+  zkp::DevBuf g1_ntt_tw;           // zkp_g1_ntt_dev: the n / 2 twiddles and 1 / n of the transform in flight (g1_ntt.hip)
   // MSM scratch
   zkp::DevBuf msm_scalars, msm_misc, var_bases;
   uint32_t* pinned = nullptr;      // pinned host landing zone for batched MSM results

@@ -58,7 +58,8 @@ const char* zkp_status_string(int32_t status);
  * then zkp_fr_powers_dev / zkp_fr_bp_t_coeffs_dev / zkp_fr_bp_lr_eval_dev / zkp_fr_ipa_fold_ab_dev (Bulletproofs R1CS prover),
  * then zkp_fr_asvc_subset_weights_dev / zkp_fr_asvc_quotient_dev (aSVC subvector commitments),
  * then zkp_pedersen_key_create / zkp_pedersen_key_free / zkp_pedersen_key_info / zkp_pedersen_commit_rows_dev / zkp_fr_vecmat_dev
- * (matrix polynomial commitments over a resident Pedersen key).
+ * (matrix polynomial commitments over a resident Pedersen key),
+ * then zkp_g1_scale_vec_dev / zkp_g1_ntt_dev (per-lane scalar multiplication and the transform over G1 points).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -525,6 +526,33 @@ int32_t zkp_pedersen_commit_rows_dev(zkp_ctx* ctx, const zkp_pedersen_key* key, 
 #define ZKP_FR_VECMAT_ROW_CHUNK 32
 int32_t zkp_fr_vecmat_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* l_dev, const uint64_t* m_dev, size_t rows, size_t cols,
                           uint64_t* out_dev);
+/* Transforms over G1 points (later in 0.7.1, detected by symbol): the primitive behind all n single-position aSVC proofs in
+ * O(n log n) (Tomescu et al. §3.4, after Feist-Khovratovich) and behind a Lagrange-form KZG / aSVC key from the powers of tau
+ * without the trapdoor.  BN254 / BLS12-381 G1.  Points: affine Montgomery words + identity flags in DEVICE memory, the layout of
+ * zkp_g1_ipa_fold_dev (16-byte aligned); a (0, 0) point is an identity too.  Every point written is the canonical affine
+ * Montgomery representative (bit-exact results), and an identity is written exactly as zkp_fixed_base_mul_g1 writes it (words and
+ * flag).  All additions are complete (equal, opposite and identity operands).  Every argument is checked before anything runs: on
+ * an error the buffers are untouched.  Both calls only launch, on the context's current stream, like zkp_fr_vec_op_dev: no host
+ * work proportional to n, no device-to-host copy.
+ *
+ * out[i] = [s_i] P_i for i < n.  inf_dev: identity flags or NULL (= none).  scalars_dev: n Fr, Montgomery, canonical, 16-byte
+ * aligned, device memory.  out_xy_dev may equal xy_dev and out_inf_dev may equal inf_dev (in place); any other overlap of an output
+ * with an input or the other output -> ZKP_ERR_BAD_ARG.  n == 0 -> ZKP_OK, nothing runs.  One launch: one lane per point; the lane
+ * reads its own scalar, recodes it into signed fixed windows and keeps its window table in LDS; one batch inversion per 64 points.
+ * ZKP_ERR_BAD_ARG: a NULL xy_dev / scalars_dev / out_xy_dev / out_inf_dev, a misaligned pointer, n > 2^31, a curve without G1
+ * support here. */
+int32_t zkp_g1_scale_vec_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy_dev, const uint8_t* inf_dev,
+                             const uint64_t* scalars_dev, size_t n, uint64_t* out_xy_dev, uint8_t* out_inf_dev);
+/* In place over 2^log_n points, natural order in and out.  op = ZKP_NTT_FFT: out[i] = sum_j [w^(i j)] P_j;
+ * op = ZKP_NTT_IFFT: out[i] = [1/n] sum_j [w^(-i j)] P_j, with w the root zkp_ntt_dev uses for the same log_n.
+ * 1 <= log_n <= ZKP_G1_NTT_MAX_LOG.  inf_dev is required: outputs can be identities whatever the inputs are.
+ * log_n + 2 launches (the twiddle table, the bit reversal, one per stage; the stage of twiddle 1 multiplies nothing), one more for
+ * the 1 / n of the inverse; one lane per butterfly (P, Q) -> (P + [w] Q, P - [w] Q), every stage ends in affine form.  The n / 2
+ * twiddles live in the context's grow-only scratch.
+ * ZKP_ERR_BAD_ARG: a NULL or misaligned xy_dev, a NULL inf_dev, inf_dev inside xy_dev, log_n outside the rule, any other op, a curve
+ * without G1 support here. */
+#define ZKP_G1_NTT_MAX_LOG 24
+int32_t zkp_g1_ntt_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* xy_dev, uint8_t* inf_dev, uint32_t log_n, int32_t op);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
