@@ -101,6 +101,12 @@ class BpVectors(C.Structure):
                 ("n", C.c_size_t), ("n_w", C.c_size_t), ("n_s", C.c_size_t), ("N", C.c_size_t)]
 
 
+class HashDesc(C.Structure):
+    """zkp_hash_desc (include/zkp_accel.h): the parameters of one MiMC / Poseidon / Rescue hash, host pointers"""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("rounds", C.c_uint32), ("alpha", C.c_uint32),
+                ("constants", vp), ("mds", vp), ("full_round", vp), ("inv_alpha", C.c_uint64 * 4)]
+
+
 MARLIN_NUM_EVALS = 21
 
 
@@ -182,6 +188,14 @@ SIGNATURES = {
     "zkp_fr_vecmat_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp]),
     "zkp_g1_scale_vec_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]),
     "zkp_g1_ntt_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, C.c_int32]),
+    "zkp_hash_params_create": (C.c_int32, [vp, C.c_int, C.POINTER(HashDesc), C.POINTER(vp)]),
+    "zkp_hash_params_free": (C.c_int32, [vp, vp]),
+    "zkp_hash_params_info": (C.c_int32, [vp, u64p]),
+    "zkp_fr_hash_blocks_dev": (C.c_int32, [vp, vp, vp, vp, C.c_size_t, vp]),
+    "zkp_fr_hash_chain_dev": (C.c_int32, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp]),
+    "zkp_fr_mimc_trace_dev": (C.c_int32, [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]),
+    "zkp_fr_merkle_tree_dev": (C.c_int32, [vp, vp, C.c_int32, vp, C.c_size_t]),
+    "zkp_fr_merkle_paths_dev": (C.c_int32, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

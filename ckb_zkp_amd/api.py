@@ -518,6 +518,55 @@ class Context:
         _lib.check(self.lib.zkp_fr_vecmat_dev(self.h, get_curve(curve).cid, C.c_void_p(l_ptr or 0), C.c_void_p(m_ptr or 0), rows, cols,
                                               C.c_void_p(out_ptr or 0)), "zkp_fr_vecmat_dev")
 
+    def hash_params_create(self, curve, kind: int, rounds: int, constants, alpha: int = 0, mds=None, full_round=None,
+                           inv_alpha: int = 0) -> int:
+        """zkp_hash_params_create: constants / mds as Montgomery Fr words ((count, 4) uint64), full_round one byte per round,
+        inv_alpha a plain integer -> params handle (free it with hash_params_free).  hashes.HashParams builds these from integers."""
+        cs = _c64(constants)
+        md = None if mds is None else _c64(mds)
+        fl = None if full_round is None else np.ascontiguousarray(full_round, dtype=np.uint8)
+        desc = _lib.HashDesc(C.sizeof(_lib.HashDesc), kind, rounds, alpha, _ptr(cs), _ptr(md), _ptr(fl),
+                             (C.c_uint64 * 4)(*[(inv_alpha >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]))
+        params = C.c_void_p()
+        _lib.check(self.lib.zkp_hash_params_create(self.h, get_curve(curve).cid, C.byref(desc), C.byref(params)), "zkp_hash_params_create")
+        return params.value
+
+    def hash_params_free(self, params: int):
+        _lib.check(self.lib.zkp_hash_params_free(self.h, C.c_void_p(params or 0)), "zkp_hash_params_free")
+
+    def hash_params_info(self, params: int) -> dict:
+        """zkp_hash_params_info -> kind, curve, rounds, device_bytes, alpha, products (Fr products of one block)"""
+        info = (C.c_uint64 * 8)()
+        _lib.check(self.lib.zkp_hash_params_info(C.c_void_p(params or 0), info), "zkp_hash_params_info")
+        return {"kind": info[0], "curve": info[1], "rounds": info[2], "device_bytes": info[3], "alpha": info[4], "products": info[5]}
+
+    def fr_hash_blocks_dev(self, params: int, xl_ptr: int, xr_ptr: int, n: int, out_ptr: int):
+        """zkp_fr_hash_blocks_dev: out[k] = block(xl[k], xr[k]) over DEVICE Montgomery Fr; out may be xl or xr.  Launches only."""
+        _lib.check(self.lib.zkp_fr_hash_blocks_dev(self.h, C.c_void_p(params or 0), C.c_void_p(xl_ptr or 0), C.c_void_p(xr_ptr or 0), n,
+                                                   C.c_void_p(out_ptr or 0)), "zkp_fr_hash_blocks_dev")
+
+    def fr_hash_chain_dev(self, params: int, msgs_ptr: int, n: int, length: int, out_ptr: int, xl_out_ptr: int = 0):
+        """zkp_fr_hash_chain_dev: the reference's `*_hash` over n row-major messages of `length` elements; out[k] the image,
+        xl_out[k] (0: not wanted) the state before the last block.  Launches only."""
+        _lib.check(self.lib.zkp_fr_hash_chain_dev(self.h, C.c_void_p(params or 0), C.c_void_p(msgs_ptr or 0), n, length,
+                                                  C.c_void_p(out_ptr or 0), C.c_void_p(xl_out_ptr or 0)), "zkp_fr_hash_chain_dev")
+
+    def fr_mimc_trace_dev(self, params: int, xl_ptr: int, xr_ptr: int, n: int, out_ptr: int, stride: int):
+        """zkp_fr_mimc_trace_dev: per block xl, xr, then (tmp, new_xl) per round at out + k * stride elements.  Launches only."""
+        _lib.check(self.lib.zkp_fr_mimc_trace_dev(self.h, C.c_void_p(params or 0), C.c_void_p(xl_ptr or 0), C.c_void_p(xr_ptr or 0), n,
+                                                  C.c_void_p(out_ptr or 0), stride), "zkp_fr_mimc_trace_dev")
+
+    def fr_merkle_tree_dev(self, params: int, merge: int, nodes_ptr: int, n: int):
+        """zkp_fr_merkle_tree_dev: fills the inner nodes [0, n - 1) of the 2 n - 1 nodes whose leaves sit at [n - 1, 2 n - 1)."""
+        _lib.check(self.lib.zkp_fr_merkle_tree_dev(self.h, C.c_void_p(params or 0), merge, C.c_void_p(nodes_ptr or 0), n),
+                   "zkp_fr_merkle_tree_dev")
+
+    def fr_merkle_paths_dev(self, nodes_ptr: int, n: int, leaf_idx_ptr: int, q: int, out_ptr: int, stride: int, len_ptr: int):
+        """zkp_fr_merkle_paths_dev: the siblings above q leaves (uint32 indices in DEVICE memory) into rows of `stride` elements and
+        their counts (0xFFFFFFFF: the index is not a leaf).  One launch."""
+        _lib.check(self.lib.zkp_fr_merkle_paths_dev(self.h, C.c_void_p(nodes_ptr or 0), n, C.c_void_p(leaf_idx_ptr or 0), q,
+                                                    C.c_void_p(out_ptr or 0), stride, C.c_void_p(len_ptr or 0)), "zkp_fr_merkle_paths_dev")
+
     def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
         """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
         Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""

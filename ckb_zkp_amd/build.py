@@ -46,7 +46,8 @@ UNITS = [("ntt.hip", "ntt.o", ["-DZKP_INLINE_MUL"]),
          ("fr_open.hip", "fr_open.o", ["-DZKP_INLINE_MUL"]),       # many polynomials at one point + linear combination of many vectors, Fr only likewise
          ("hyrax.hip", "hyrax.o", ["-DZKP_INLINE_MUL"]),           # Hyrax data-parallel GKR: sum-check over the copies + batched layer evaluation, Fr only likewise
          ("bulletproofs.hip", "bulletproofs.o", ["-DZKP_INLINE_MUL"]),   # Bulletproofs R1CS prover: powers, fused l(X) / r(X) + IPA a / b fold, Fr only likewise
-         ("asvc.hip", "asvc.o", ["-DZKP_INLINE_MUL"])]             # aSVC: subset weights + the quotient by a subvector's vanishing polynomial, Fr only likewise
+         ("asvc.hip", "asvc.o", ["-DZKP_INLINE_MUL"]),             # aSVC: subset weights + the quotient by a subvector's vanishing polynomial, Fr only likewise
+         ("fr_hash.hip", "fr_hash.o", ["-DZKP_INLINE_MUL"])]       # MiMC / Poseidon / Rescue permutations, one lane per block, + CBMT Merkle trees, Fr only likewise
 for _c, _g in CONFIGS:
     _d = [f"-DZKP_CFG_CURVE={_c}", f"-DZKP_CFG_GROUP={_g}"]
     UNITS.append(("msm_group.hip", f"msm_group_c{_c}{_g}.o", _d + (["-DZKP_INLINE_MUL"] if (_c, _g) in ((0, 1), (0, 2), (1, 1)) else [])))

@@ -12,6 +12,7 @@
 #include "hyrax.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
+#include "fr_hash.hpp"
 #include "fr_open.hpp"
 #include "g1_ntt.hpp"
 #include "pedersen.hpp"
@@ -932,6 +933,43 @@ int32_t zkp_g1_scale_vec_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy
 int32_t zkp_g1_ntt_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* xy_dev, uint8_t* inf_dev, uint32_t log_n, int32_t op) {
   if (!xy_dev || !inf_dev) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { g1_ntt_vtbl(curve)->ntt(ctx, xy_dev, inf_dev, log_n, op); });
+}
+int32_t zkp_hash_params_create(zkp_ctx* ctx, zkp_curve_t curve, const zkp_hash_desc* desc, zkp_hash_params** out) {
+  if (!desc || !out) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { hash_params_create(ctx, curve, desc, out); });
+}
+int32_t zkp_hash_params_free(zkp_ctx* ctx, zkp_hash_params* params) {
+  if (!params) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { hash_params_free(ctx, params); });
+}
+int32_t zkp_hash_params_info(const zkp_hash_params* params, uint64_t* info) {
+  if (!params || !info) return ZKP_ERR_BAD_ARG;
+  hash_params_info(params, info);
+  return ZKP_OK;
+}
+int32_t zkp_fr_hash_blocks_dev(zkp_ctx* ctx, const zkp_hash_params* params, const uint64_t* xl_dev, const uint64_t* xr_dev, size_t n,
+                               uint64_t* out_dev) {
+  if (!params || !xl_dev || !xr_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_hash_blocks(ctx, params, xl_dev, xr_dev, n, out_dev); });
+}
+int32_t zkp_fr_hash_chain_dev(zkp_ctx* ctx, const zkp_hash_params* params, const uint64_t* msgs_dev, size_t n, size_t len,
+                              uint64_t* out_dev, uint64_t* xl_out_dev) {
+  if (!params || !msgs_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_hash_chain(ctx, params, msgs_dev, n, len, out_dev, xl_out_dev); });
+}
+int32_t zkp_fr_mimc_trace_dev(zkp_ctx* ctx, const zkp_hash_params* params, const uint64_t* xl_dev, const uint64_t* xr_dev, size_t n,
+                              uint64_t* out_dev, size_t stride) {
+  if (!params || !xl_dev || !xr_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_mimc_trace(ctx, params, xl_dev, xr_dev, n, out_dev, stride); });
+}
+int32_t zkp_fr_merkle_tree_dev(zkp_ctx* ctx, const zkp_hash_params* params, int32_t merge, uint64_t* nodes_dev, size_t n) {
+  if (!params || !nodes_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_merkle_tree(ctx, params, merge, nodes_dev, n); });
+}
+int32_t zkp_fr_merkle_paths_dev(zkp_ctx* ctx, const uint64_t* nodes_dev, size_t n, const uint32_t* leaf_idx_dev, size_t q,
+                                uint64_t* out_dev, size_t stride, uint32_t* len_dev) {
+  if (!nodes_dev || !leaf_idx_dev || !out_dev || !len_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_merkle_paths(ctx, nodes_dev, n, leaf_idx_dev, q, out_dev, stride, len_dev); });
 }
 int32_t zkp_bench_mulmod(zkp_ctx* ctx, zkp_curve_t curve, int32_t field, int32_t unsaturated, double* out) {
   if (!out || (curve != ZKP_BN254 && curve != ZKP_BLS12_381) || field < 0 || field > 1) return ZKP_ERR_BAD_ARG;

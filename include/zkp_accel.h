@@ -59,7 +59,9 @@ const char* zkp_status_string(int32_t status);
  * then zkp_fr_asvc_subset_weights_dev / zkp_fr_asvc_quotient_dev (aSVC subvector commitments),
  * then zkp_pedersen_key_create / zkp_pedersen_key_free / zkp_pedersen_key_info / zkp_pedersen_commit_rows_dev / zkp_fr_vecmat_dev
  * (matrix polynomial commitments over a resident Pedersen key),
- * then zkp_g1_scale_vec_dev / zkp_g1_ntt_dev (per-lane scalar multiplication and the transform over G1 points).
+ * then zkp_g1_scale_vec_dev / zkp_g1_ntt_dev (per-lane scalar multiplication and the transform over G1 points),
+ * then zkp_hash_params_create / zkp_hash_params_free / zkp_hash_params_info / zkp_fr_hash_blocks_dev / zkp_fr_hash_chain_dev /
+ * zkp_fr_mimc_trace_dev / zkp_fr_merkle_tree_dev / zkp_fr_merkle_paths_dev (MiMC, Poseidon and Rescue hashing, CBMT Merkle trees).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -553,6 +555,97 @@ int32_t zkp_g1_scale_vec_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy
  * without G1 support here. */
 #define ZKP_G1_NTT_MAX_LOG 24
 int32_t zkp_g1_ntt_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* xy_dev, uint8_t* inf_dev, uint32_t log_n, int32_t op);
+/* Algebraic hashes and complete binary Merkle trees (later in 0.7.1, detected by symbol): the `*_block` / `*_hash` functions of
+ * gadgets/src/hashes/{mimc,poseidon,rescue}.rs and the tree of gadgets/src/merkletree/cbmt.rs, i.e. the values that the reference's
+ * hash and membership circuits (cli/src/circuits/hash.rs, gadgets/src/merkletree/cbmt_constraints.rs, marlin/examples/mimc.rs)
+ * assign.  The producer of a device-resident witness for zkp_groth16_prove_dev.  Fr of BN254 / BLS12-381; state width
+ * ZKP_HASH_WIDTH = 3 (rate 2, capacity 1), the reference's M.  The library ships NO constant table: every round constant, matrix
+ * and exponent is the caller's (the reference's Poseidon / Rescue tables are literals of its source, its MiMC constants come from
+ * a seeded generator).
+ *
+ * zkp_hash_desc: the parameters of one hash.  Field elements: Fr, Montgomery, < r, HOST memory, 4 x u64 each.
+ *   ZKP_HASH_MIMC      rounds 1..ZKP_HASH_MAX_ROUNDS_MIMC; constants[rounds].  The block is mimc_block (mimc.rs:49-62): per round
+ *                      t = xl + c_i, (xl, xr) <- (t^3 + xr, xl); the result is xl.  alpha, mds, full_round, inv_alpha: ignored.
+ *   ZKP_HASH_POSEIDON  rounds 1..ZKP_HASH_MAX_ROUNDS_POSEIDON; alpha 3, 5 or 7; constants = ark[rounds][3]; mds[3][3] row-major;
+ *                      full_round[rounds], one byte per round (0 = partial).  The block is poseidon_block (poseidon.rs:553-585):
+ *                      state (xl, xr, 0); per round state += ark[i], x^alpha on all three elements (full) or on element 2 only
+ *                      (partial), state <- mds state; the result is state[0].  The per-round flag expresses both the reference's
+ *                      schedule (:560 makes exactly round RF / 2 partial) and the standard RF / 2 full, RP partial, RF / 2 full.
+ *   ZKP_HASH_RESCUE    rounds R 1..ZKP_HASH_MAX_ROUNDS_RESCUE; alpha 3, 5 or 7; inv_alpha: a plain 256-bit integer, little-endian
+ *                      words, not zero; constants[2 R + 1][3]; mds[3][3].  The block is rescue_block (rescue.rs:337-367): state
+ *                      (xl, xr, 0) + constants[0]; for i < 2 R: x^alpha (i even) or x^inv_alpha (i odd) on all three elements,
+ *                      state <- mds state + constants[i + 1]; the result is state[0].  At creation a one-lane kernel checks
+ *                      (x^alpha)^inv_alpha == x for the fixed x = 2, 3 (and 5): a mismatch -> ZKP_ERR_BAD_ARG and no handle.
+ * zkp_hash_params_create copies the constants once to device memory the handle owns, on the context's current stream, and returns
+ * when they are there.  A handle belongs to the context that created it: every entry that is given one of another context returns
+ * ZKP_ERR_BAD_ARG; zkp_hash_params_free waits for that context's current stream first.  ZKP_ERR_BAD_ARG: struct_size smaller than
+ * the struct, an unknown kind, rounds or alpha out of range, a NULL table the kind needs, an element >= r, inv_alpha == 0, the
+ * Rescue check; on an error *out is untouched.
+ * zkp_hash_params_info: info[0] kind, [1] curve, [2] rounds, [3] device bytes held, [4] alpha (0 for MiMC), [5] Fr products of one
+ * block by the schedule, [6] and [7] 0. */
+#define ZKP_HASH_WIDTH 3
+#define ZKP_HASH_MAX_ROUNDS_MIMC 512
+#define ZKP_HASH_MAX_ROUNDS_POSEIDON 128
+#define ZKP_HASH_MAX_ROUNDS_RESCUE 64
+#define ZKP_HASH_MAX_LOG_BLOCKS 28
+#define ZKP_HASH_MAX_LOG_LEAVES 27
+typedef enum { ZKP_HASH_MIMC = 0, ZKP_HASH_POSEIDON = 1, ZKP_HASH_RESCUE = 2 } zkp_hash_kind;
+typedef enum { ZKP_MERGE_BLOCK = 0, ZKP_MERGE_CHAIN = 1 } zkp_merge;
+typedef struct {
+  uint32_t struct_size;        /* sizeof(zkp_hash_desc) as the caller compiled it */
+  int32_t kind;                /* zkp_hash_kind */
+  uint32_t rounds;
+  uint32_t alpha;
+  const uint64_t* constants;   /* MiMC: rounds; Poseidon: rounds x 3; Rescue: (2 rounds + 1) x 3 */
+  const uint64_t* mds;         /* 3 x 3, row-major (Poseidon, Rescue) */
+  const uint8_t* full_round;   /* rounds bytes (Poseidon) */
+  uint64_t inv_alpha[4];       /* (Rescue) */
+} zkp_hash_desc;
+typedef struct zkp_hash_params zkp_hash_params;
+int32_t zkp_hash_params_create(zkp_ctx* ctx, zkp_curve_t curve, const zkp_hash_desc* desc, zkp_hash_params** out);
+int32_t zkp_hash_params_free(zkp_ctx* ctx, zkp_hash_params* params);
+int32_t zkp_hash_params_info(const zkp_hash_params* params, uint64_t* info);
+/* The batched permutations: one lane per block, the whole permutation in registers, the constants through wave-uniform loads.
+ * Vectors: Fr, Montgomery, canonical, 16-byte aligned, DEVICE memory; every element written is the canonical Montgomery
+ * representative (bit-exact results).  Every argument is checked before anything runs: on an error the outputs are untouched.
+ * All of them run on the context's current stream and only launch, like zkp_fr_vec_op_dev: no host work proportional to n.
+ *
+ * out[k] = block(xl[k], xr[k]) for k < n, 1 <= n <= 2^ZKP_HASH_MAX_LOG_BLOCKS.  out_dev may be xl_dev or xr_dev itself; any other
+ * overlap of out with an input -> ZKP_ERR_BAD_ARG.  One launch. */
+int32_t zkp_fr_hash_blocks_dev(zkp_ctx* ctx, const zkp_hash_params* params, const uint64_t* xl_dev, const uint64_t* xr_dev, size_t n,
+                               uint64_t* out_dev);
+/* The reference's `*_hash` (mimc.rs:78-90, poseidon.rs:601-613, rescue.rs:383-395) over n messages of len elements each, row-major
+ * in msgs_dev: h = 0, then h <- block(h, m[k len + j]) for j < len; out[k] is the image and xl_out[k] (xl_out_dev may be NULL) is h
+ * before the last block, the `xl` that the gadget allocates (`*_hash` returns (xl, xr, image); xr is the last message element).
+ * n >= 1, len >= 1, n len <= 2^ZKP_HASH_MAX_LOG_BLOCKS.  The outputs overlap neither the messages nor each other.  One launch. */
+int32_t zkp_fr_hash_chain_dev(zkp_ctx* ctx, const zkp_hash_params* params, const uint64_t* msgs_dev, size_t n, size_t len,
+                              uint64_t* out_dev, uint64_t* xl_out_dev);
+/* MiMC only (another kind -> ZKP_ERR_BAD_ARG): the auxiliary assignment of the `mimc` gadget (mimc.rs:110-157) in its allocation
+ * order.  For block k, 2 rounds + 2 elements at out + k stride: xl, xr, then per round tmp_i = (xl_i + c_i)^2 and new_xl_i.
+ * 1 <= n <= 2^ZKP_HASH_MAX_LOG_BLOCKS, stride >= 2 rounds + 2, n stride <= 2^32; the elements of a gap between two blocks are not
+ * written.  out overlaps neither input.  With 5 rounds and stride 12 at z_dev + 32 bytes this is the whole auxiliary assignment of
+ * marlin/examples/mimc.rs.  One launch. */
+int32_t zkp_fr_mimc_trace_dev(zkp_ctx* ctx, const zkp_hash_params* params, const uint64_t* xl_dev, const uint64_t* xr_dev, size_t n,
+                              uint64_t* out_dev, size_t stride);
+/* The complete binary Merkle tree of cbmt.rs (:182-202): nodes_dev holds 2 n - 1 Fr with the n leaves already at [n - 1, 2 n - 1);
+ * the call fills [0, n - 1) with nodes[i] = merge(nodes[2 i + 1], nodes[2 i + 2]); nodes[0] is the root.  Any 1 <= n <=
+ * 2^ZKP_HASH_MAX_LOG_LEAVES, not only powers of two; n == 1 launches nothing.  merge: ZKP_MERGE_BLOCK = block(l, r);
+ * ZKP_MERGE_CHAIN = block(block(0, l), r), the reference's hash(l || r) (MergeMimc, cbmt_constraints.rs:146-155).
+ * With depth(i) = floor(log2(i + 1)) and D = depth(n - 2): one launch per depth D, ..., 9, one lane per node, then ONE workgroup of
+ * 256 lanes for the depths 8 .. 0 with a barrier between them: max(0, D - 8) + 1 launches. */
+int32_t zkp_fr_merkle_tree_dev(zkp_ctx* ctx, const zkp_hash_params* params, int32_t merge, uint64_t* nodes_dev, size_t n);
+/* build_proof (cbmt.rs:31-72) for q leaves at once: for leaf_idx_dev[k] (uint32, device memory, any order, repeats allowed) the
+ * siblings from heap index n - 1 + leaf upwards, the root excluded, go to out + k stride and their count, depth(n - 1 + leaf), to
+ * len_dev[k]; the elements from the count up to stride are zeroed.  stride >= depth(2 n - 2); n == 1 gives length 0.  A leaf
+ * index >= n gives len_dev[k] = ZKP_MERKLE_BAD_LEAF and a zeroed row, and reads nothing outside nodes_dev.  1 <= n <=
+ * 2^ZKP_HASH_MAX_LOG_LEAVES, 1 <= q <= 2^ZKP_HASH_MAX_LOG_BLOCKS, q max(stride, 1) <= 2^32.  The outputs overlap neither the inputs
+ * nor each other.  One gather launch, no arithmetic: the curve does not enter.
+ * ZKP_ERR_BAD_ARG of the five entries above: a NULL or misaligned pointer (leaf_idx_dev / len_dev: 4 bytes), a count of 0 or above
+ * its cap, a stride too small, an unknown merge, a params handle of another context or (trace) of another kind, spans that overlap
+ * against the rules. */
+#define ZKP_MERKLE_BAD_LEAF 4294967295u
+int32_t zkp_fr_merkle_paths_dev(zkp_ctx* ctx, const uint64_t* nodes_dev, size_t n, const uint32_t* leaf_idx_dev, size_t q,
+                                uint64_t* out_dev, size_t stride, uint32_t* len_dev);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,

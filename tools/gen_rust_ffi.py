@@ -14,9 +14,9 @@ HDR = (ROOT / "include" / "zkp_accel.h").read_text()
 
 SCALAR = {"int32_t": "i32", "int64_t": "i64", "uint32_t": "u32", "uint64_t": "u64", "size_t": "usize", "int": "c_int", "float": "f32",
           "double": "f64", "uint8_t": "u8", "void": "c_void", "char": "c_char", "zkp_curve_t": "c_int"}
-OPAQUE = ["zkp_ctx", "zkp_groth16_pk", "zkp_groth16_pk_multi", "zkp_fs_rng", "zkp_marlin_index", "zkp_gkr_layer", "zkp_pedersen_key"]
+OPAQUE = ["zkp_ctx", "zkp_groth16_pk", "zkp_groth16_pk_multi", "zkp_fs_rng", "zkp_marlin_index", "zkp_gkr_layer", "zkp_pedersen_key", "zkp_hash_params"]
 STRUCTS = ["zkp_ctx_config", "zkp_csr", "zkp_groth16_pk_desc", "zkp_marlin_index_desc", "zkp_marlin_rand", "zkp_marlin_proof",
-           "zkp_groth16_timing", "zkp_marlin_timing"]
+           "zkp_groth16_timing", "zkp_marlin_timing", "zkp_hash_desc"]
 
 
 def strip_comments(t):
