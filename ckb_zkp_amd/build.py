@@ -35,6 +35,7 @@ UNITS = [("ntt.hip", "ntt.o", ["-DZKP_INLINE_MUL"]),
          ("poly.hip", "poly.o", ["-DZKP_INLINE_MUL"]),
          ("msm.hip", "msm.o", []),
          ("groth16.hip", "groth16.o", ["-DZKP_INLINE_MUL"]),
+         ("groth16_key.hip", "groth16_key.o", ["-DZKP_INLINE_MUL"]),   # the Groth16 key: upload phase by phase, evaluation-form transforms + C fold, info, release
          ("capi.hip", "capi.o", []),
          ("bench_kern.hip", "bench_kern.o", ["-DZKP_INLINE_MUL"] + UNROLL),
          ("fs_rng.cpp", "fs_rng.o", []),

@@ -140,7 +140,7 @@ struct zkp_cfg {
   long long msm_chunk = (long long)3 << 19;   // 0: never chunk
   double table_budget_gb = 0;         // 0: free device memory minus a quarter of the device
   bool h_lagrange = true, c_fold = true, host_affine = true;
-  long long lfold_heavy_cost = 0;     // 0: chosen per key (groth16.hip fold_c_into_l)
+  long long lfold_heavy_cost = 0;     // 0: chosen per key (groth16_key.hip fold_c_into_l)
   int multi_exchange = 0;             // ZKP_EXCHANGE_*
   int multi_exchange_timeout_ms = 30000;
   int multi_wm_split = -1;            // -1: measured per key; 0 / 1 forced

@@ -687,7 +687,7 @@ __global__ __launch_bounds__(128) void fixed_base_kernel(const uint32_t* base, c
 
 
 // ------------------------------------------------------------------------------------------- group-element transform
-// The H query in EVALUATION form (groth16.hip, round 4): H'_j = (1/N) sum_i w^(-ij) g^(-i) H_i, so that
+// The H query in EVALUATION form (groth16_key.hip, round 4): H'_j = (1/N) sum_i w^(-ij) g^(-i) H_i, so that
 // sum_j v_j H'_j = sum_i h_i H_i for h = coset_ifft(v) — the last transform of the witness map (r1cs_to_qap.rs:169) moves into the key.
 // A radix-2 decimation-in-time transform over group elements: butterflies (u, q) -> (u + t q, u - t q) with t a scalar; one-time
 // work per key (N log N / 2 scalar multiplications), plain double-and-add on the saturated formulas of ec_dev.hpp.
@@ -776,7 +776,7 @@ __global__ __launch_bounds__(128) void gfft_affine_kernel(const char* __restrict
 }
 #endif
 
-// out_m = L_m - sum_{e in column m of C} coeff_e * G_{row_e}: the C matrix folded into the L query (groth16.hip).  One lane per
+// out_m = L_m - sum_{e in column m of C} coeff_e * G_{row_e}: the C matrix folded into the L query (groth16_key.hip).  One lane per
 // variable; kind[e]: 1 = coefficient +1, 2 = coefficient -1, 0 = coeff[e] (Montgomery, 8 words) by double-and-add.  One-time work.
 #if ZKP_CFG_GROUP == 1
 template <class F, int BITS>

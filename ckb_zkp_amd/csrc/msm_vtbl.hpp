@@ -94,7 +94,7 @@ struct MsmVtbl {
   // the root, each level stored directly behind its predecessor.  With `sets` > 1 (pair_top_segsum) the level at `base` holds the
   // sets side by side; set g's first output level goes to base + (sets + g) * count, a region of its own, the rest behind it
   void (*pair_top)(hipStream_t, char* base, uint32_t count);
-  // group-element transform of a base vector (msm_group.hip "group-element transform"; groth16.hip: the H query in evaluation form):
+  // group-element transform of a base vector (msm_group.hip "group-element transform"; groth16_key.hip: the H query in evaluation form):
   // out_j = sum_i tw^(ij) (scal_i * P_i), i, j < 2^log_n; scal / tw: canonical 8-word scalars (tw: 2^(log_n-1) powers);
   // X: 2^log_n XYZZ points of scratch
   void (*gfft)(hipStream_t, const char* xy, const uint8_t* inf, size_t n_in, const uint32_t* scal, const uint32_t* tw, uint32_t log_n,

@@ -32,7 +32,7 @@ constexpr int tune_task_cap(int v) { return v < 4 ? 0 : v > TUNE_TASK_CAP_MAX ? 
   FLAG(ntt_v2, "ZKP_NTT_V2", true, "unsaturated-limb NTT pass kernel; 0: the saturated one")                                              \
   FLAG(ntt_full, "ZKP_NTT_FULL", true, "full-size twiddle / coset tables; 0: two-level lookups")                                          \
   FLAG(ntt_fuse, "ZKP_NTT_FUSE", true, "witness-map transforms as fused pass chains; 0: separate transforms")                             \
-  /* groth16.hip: key upload */                                                                                                           \
+  /* groth16_key.hip: key upload */                                                                                                       \
   FLAG(b_window, "ZKP_B_WINDOW", false, "B queries get window bits of their own, sized by their live bases")                              \
   INT (b_window_bits, "ZKP_B_WINDOW_BITS", -1, v < 0 ? 0 : v, "with ZKP_B_WINDOW: their window bits; unset: round(log2 live) - 2")        \
   INT (b_task_cap, "ZKP_B_TASK_CAP", -1, v < 0 ? 0 : v, "with ZKP_B_WINDOW: their entries per task; unset: 32")                           \

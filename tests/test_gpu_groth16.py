@@ -568,3 +568,98 @@ def test_identity_proof_points_through_the_host_tail(ctx, curve):
         pk.free()
     assert list(inf) == [1, 1, 1] and not out.any()
     assert not outs.any() and infs.tolist() == [[1, 1, 1]] * 3
+
+
+def _key_plans(ctx):
+    """name -> the eight words of zkp_groth16_pk_info for the five keys of test_key_plan_is_unchanged"""
+    import ctypes as C
+    from ckb_zkp_amd import _lib
+    from ckb_zkp_amd.api import Context
+    from ckb_zkp_amd.circuits import samples_for_domain
+    from ckb_zkp_amd.r1cs import ConstraintSystem, R1csInstance
+    from tests.test_gpu_fuzz import _DenseColumnCircuit
+
+    def words(on, params, inst, **kw):
+        pk = groth16.ProvingKey(on, params, inst, **kw)
+        try:
+            info = (C.c_uint64 * 8)()
+            _lib.check(on.lib.zkp_groth16_pk_info(on.h, pk.h, info), "zkp_groth16_pk_info")
+            return [int(w) for w in info]
+        finally:
+            pk.free()
+
+    plans = {}
+    inst = mimc_chain_instance("bn254", samples_for_domain(11))
+    params = groth16.generate_parameters(ctx, "bn254", inst, **TOXIC)
+    plans["bn254_k11"] = words(ctx, params, inst)
+    plans["bn254_k11_keep_form"] = words(ctx, params, inst, keep_form=True)
+    for rank in (0, 1):
+        plans[f"bn254_k11_shard_{rank}_of_2"] = words(ctx, params, inst, shard=(rank, 2))
+    inst = mimc_chain_instance("bls12_381", samples_for_domain(9))
+    plans["bls12_381_k9"] = words(ctx, groth16.generate_parameters(ctx, "bls12_381", inst, **TOXIC), inst)
+    cs = ConstraintSystem(groth16.get_curve("bn254"), True)
+    _DenseColumnCircuit("bn254", 4242 + 300, 300).generate_constraints(cs)
+    inst = R1csInstance.from_cs(cs)
+    own = Context(ctx.device, dict(c_fold_heavy_cost=3))
+    try:
+        plans["bn254_dense_column_300_heavy_cost_3"] = words(own, groth16.generate_parameters(ctx, "bn254", inst, **TOXIC), inst)
+    finally:
+        own.close()
+    return plans
+
+
+def test_key_plan_is_unchanged(ctx):
+    """Window group, table bytes, window bits and count, table copies, B window bits, the sort-sharing word and the key-form word of
+    zkp_groth16_pk_info for five keys — the 2^11 MiMC chain on BN254 as uploaded by default, kept as given, and sharded over two ranks;
+    the 2^9 chain on BLS12-381; a key with dense C columns whose fold sends nearly every column through the heavy path — equal
+    tests/golden/groth16_key_plan.json, recorded with this body before the upload was split into KeyBuild's phases
+    (csrc/groth16_key.hip).  All five are far below any table budget: free device memory does not enter the plan."""
+    import json
+    from pathlib import Path
+    want = json.loads((Path(__file__).resolve().parent / "golden" / "groth16_key_plan.json").read_text())
+    got = _key_plans(ctx)
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name
+
+
+def test_failed_upload_releases_its_tables(ctx):
+    """An upload that fails late gives back what it had made resident.  The 2^11 BN254 key with one entry of C's column array set to
+    nz: the fold refuses it (ZKP_ERR_BAD_ARG, an argument rule checked on the host before any kernel reads the array) after the A,
+    B1, B2 and H tables are resident.  After a first failing upload (the context's scratch reaches its size) three more must not
+    lower the free device memory by as much as one key's tables; with a leak each of them costs four of the five tables.  Free
+    memory is read with hipMemGetInfo of the HIP runtime the library itself is linked to (looked up through the library's handle):
+    torch.cuda, initialised in a process whose device that runtime already holds, finds no device."""
+    import ctypes as C
+    from ckb_zkp_amd.circuits import samples_for_domain
+    inst = mimc_chain_instance("bn254", samples_for_domain(11))
+    params = groth16.generate_parameters(ctx, "bn254", inst, **TOXIC)
+    pk = groth16.ProvingKey(ctx, params, inst)
+    try:
+        assert pk.table_plan()["c_folded_into_l"]
+        table_bytes = pk.table_plan()["table_bytes"]
+    finally:
+        pk.free()
+    assert table_bytes > 0
+    d, keep = groth16._fill_desc(params, inst)
+    col = next(a for a in keep if a.ctypes.data == d.ct.col)
+    col[len(col) // 2] = inst.num_inputs + inst.num_aux
+
+    def failing_upload():
+        h = C.c_void_p()
+        assert ctx.lib.zkp_groth16_pk_upload(ctx.h, C.byref(d), C.byref(h)) == -1                # ZKP_ERR_BAD_ARG
+        assert not h.value
+
+    def free_bytes():
+        dev, free, total = C.c_int(-1), C.c_size_t(), C.c_size_t()
+        assert ctx.lib.hipGetDevice(C.byref(dev)) == 0 and dev.value == ctx.device
+        assert ctx.lib.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+        return free.value
+
+    failing_upload()
+    free_before = free_bytes()
+    for _ in range(3):
+        failing_upload()
+    drop = free_before - free_bytes()
+    print(f"three failed uploads: free device memory fell by {drop} bytes; one key's tables: {table_bytes} bytes")
+    assert drop < table_bytes
