@@ -188,6 +188,12 @@ SIGNATURES = {
     "zkp_fr_vecmat_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp]),
     "zkp_g1_scale_vec_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]),
     "zkp_g1_ntt_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, C.c_int32]),
+    "zkp_pairing_info": (C.c_int32, [C.c_int, u64p]),
+    "zkp_pairing_miller_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp]),
+    "zkp_pairing_final_exp_dev": (C.c_int32, [vp, C.c_int, vp, C.c_size_t, vp]),
+    "zkp_pairing_product_is_one_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp]),
+    "zkp_pairing": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]),
+    "zkp_pairing_check": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp]),
     "zkp_hash_params_create": (C.c_int32, [vp, C.c_int, C.POINTER(HashDesc), C.POINTER(vp)]),
     "zkp_hash_params_free": (C.c_int32, [vp, vp]),
     "zkp_hash_params_info": (C.c_int32, [vp, u64p]),

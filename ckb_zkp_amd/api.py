@@ -280,6 +280,60 @@ class Context:
         assert n >= 2 and n & (n - 1) == 0
         return self._g1_points_run(xy, inf, [], lambda d, di: self.g1_ntt_dev(curve, d, di, n.bit_length() - 1, op))
 
+    # ---- optimal-ate pairings (ark-ec PairingEngine::{miller_loop, final_exponentiation, product_of_pairings})
+    def pairing_info(self, curve) -> dict:
+        """zkp_pairing_info: the power k of the final exponentiation's contract and the launch shape (no device work)."""
+        info = (C.c_uint64 * 8)()
+        _lib.check(self.lib.zkp_pairing_info(get_curve(curve).cid, info), "zkp_pairing_info")
+        return dict(gt_power=info[0], fq12_words=info[1], pairs_per_workgroup=info[2], max_n=info[3], lds_bytes=info[4])
+
+    def pairing_miller_dev(self, curve, g1_xy_dev: int, g1_inf_dev: int, g2_xy_dev: int, g2_inf_dev: int, n: int, group: int,
+                           out_f12_dev: int):
+        """zkp_pairing_miller_dev: out[j] = the product of the Miller functions of group j's pairs, over DEVICE pointers (affine
+        Montgomery points + identity flags, both flag arrays required; n / group Fq12 out).  Launches only."""
+        _lib.check(self.lib.zkp_pairing_miller_dev(self.h, get_curve(curve).cid, C.c_void_p(g1_xy_dev or 0), C.c_void_p(g1_inf_dev or 0),
+                                                   C.c_void_p(g2_xy_dev or 0), C.c_void_p(g2_inf_dev or 0), n, group,
+                                                   C.c_void_p(out_f12_dev or 0)), "zkp_pairing_miller_dev")
+
+    def pairing_final_exp_dev(self, curve, f12_dev: int, m: int, out_gt_dev: int):
+        """zkp_pairing_final_exp_dev: out[e] = f[e]^(k (q^12 - 1) / r) over m DEVICE Fq12 (out may be the input).  Launches only."""
+        _lib.check(self.lib.zkp_pairing_final_exp_dev(self.h, get_curve(curve).cid, C.c_void_p(f12_dev or 0), m,
+                                                      C.c_void_p(out_gt_dev or 0)), "zkp_pairing_final_exp_dev")
+
+    def pairing_product_is_one_dev(self, curve, g1_xy_dev: int, g1_inf_dev: int, g2_xy_dev: int, g2_inf_dev: int, n: int, group: int,
+                                   ok_dev: int):
+        """zkp_pairing_product_is_one_dev: ok[j] = 1 iff the product of group j's pairings is one (n / group bytes).  Launches only."""
+        _lib.check(self.lib.zkp_pairing_product_is_one_dev(self.h, get_curve(curve).cid, C.c_void_p(g1_xy_dev or 0),
+                                                           C.c_void_p(g1_inf_dev or 0), C.c_void_p(g2_xy_dev or 0),
+                                                           C.c_void_p(g2_inf_dev or 0), n, group, C.c_void_p(ok_dev or 0)),
+                   "zkp_pairing_product_is_one_dev")
+
+    def _pairing_args(self, c, g1_xy, g1_inf, g2_xy, g2_inf):
+        g1, g2 = _c64(g1_xy).reshape(-1, 2 * c.fq_limbs), _c64(g2_xy).reshape(-1, 4 * c.fq_limbs)
+        n = g1.shape[0]
+        assert g2.shape[0] == n
+        i1 = np.zeros(n, dtype=np.uint8) if g1_inf is None else np.ascontiguousarray(g1_inf, dtype=np.uint8)
+        i2 = np.zeros(n, dtype=np.uint8) if g2_inf is None else np.ascontiguousarray(g2_inf, dtype=np.uint8)
+        assert i1.shape == (n,) and i2.shape == (n,)
+        return g1, i1, g2, i2, n
+
+    def pairing(self, curve, g1_xy, g1_inf, g2_xy, g2_inf) -> np.ndarray:
+        """zkp_pairing: (n, 12 * fq_limbs) uint64, row i = e(P_i, Q_i)^k as Montgomery words (flags None = no identities)."""
+        c = get_curve(curve)
+        g1, i1, g2, i2, n = self._pairing_args(c, g1_xy, g1_inf, g2_xy, g2_inf)
+        out = np.zeros((n, 12 * c.fq_limbs), dtype=np.uint64)
+        _lib.check(self.lib.zkp_pairing(self.h, c.cid, _ptr(g1), _ptr(i1), _ptr(g2), _ptr(i2), n, _ptr(out)), "zkp_pairing")
+        return out
+
+    def pairing_check(self, curve, g1_xy, g1_inf, g2_xy, g2_inf, group: int) -> np.ndarray:
+        """zkp_pairing_check: (n / group,) uint8, entry j = 1 iff the product of group j's pairings is one."""
+        c = get_curve(curve)
+        g1, i1, g2, i2, n = self._pairing_args(c, g1_xy, g1_inf, g2_xy, g2_inf)
+        ok = np.zeros(n // group if group and n % group == 0 else 1, dtype=np.uint8)
+        _lib.check(self.lib.zkp_pairing_check(self.h, c.cid, _ptr(g1), _ptr(i1), _ptr(g2), _ptr(i2), n, group, _ptr(ok)),
+                   "zkp_pairing_check")
+        return ok
+
     def fr_dot_batch_dev(self, curve, a_ptrs, b_ptrs, ns) -> np.ndarray:
         """zkp_fr_dot_batch_dev: <a_k, b_k> over DEVICE Fr vectors (Montgomery) -> (count, 4) uint64 Montgomery."""
         k = len(ns)

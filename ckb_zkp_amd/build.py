@@ -65,6 +65,7 @@ for _c in (0, 1):
     UNITS.append(("ipa.hip", f"ipa_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"] + UNROLL))       # IPA generator fold, G1 (own launch table)
     UNITS.append(("pedersen.hip", f"pedersen_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"] + UNROLL))   # resident Pedersen key, row commitments + Fr vector-matrix product, G1 (own launch table)
     UNITS.append(("g1_ntt.hip", f"g1_ntt_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"] + UNROLL))   # per-lane scalar multiplication + the transform over G1 points (own launch table)
+    UNITS.append(("pairing.hip", f"pairing_c{_c}.o", [f"-DZKP_CFG_CURVE={_c}"]))          # optimal-ate Miller products + final exponentiation (own launch table); never ZKP_INLINE_MUL
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result",
          "-ffp-contract=off"]
 

@@ -12,6 +12,7 @@
 #include "hyrax.hpp"
 #include "internal.hpp"
 #include "ipa.hpp"
+#include "pairing.hpp"
 #include "fr_hash.hpp"
 #include "fr_open.hpp"
 #include "g1_ntt.hpp"
@@ -933,6 +934,35 @@ int32_t zkp_g1_scale_vec_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* xy
 int32_t zkp_g1_ntt_dev(zkp_ctx* ctx, zkp_curve_t curve, uint64_t* xy_dev, uint8_t* inf_dev, uint32_t log_n, int32_t op) {
   if (!xy_dev || !inf_dev) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { g1_ntt_vtbl(curve)->ntt(ctx, xy_dev, inf_dev, log_n, op); });
+}
+int32_t zkp_pairing_info(zkp_curve_t curve, uint64_t* info) {
+  if (!info || (curve != ZKP_BN254 && curve != ZKP_BLS12_381)) return ZKP_ERR_BAD_ARG;
+  pairing_vtbl(curve)->info(info);
+  return ZKP_OK;
+}
+int32_t zkp_pairing_miller_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy_dev, const uint8_t* g1_inf_dev,
+                               const uint64_t* g2_xy_dev, const uint8_t* g2_inf_dev, size_t n, size_t group, uint64_t* out_f12_dev) {
+  if (!g1_xy_dev || !g1_inf_dev || !g2_xy_dev || !g2_inf_dev || !out_f12_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pairing_vtbl(curve)->miller(ctx, g1_xy_dev, g1_inf_dev, g2_xy_dev, g2_inf_dev, n, group, out_f12_dev); });
+}
+int32_t zkp_pairing_final_exp_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* f12_dev, size_t m, uint64_t* out_gt_dev) {
+  if (!f12_dev || !out_gt_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pairing_vtbl(curve)->final_exp(ctx, f12_dev, m, out_gt_dev); });
+}
+int32_t zkp_pairing_product_is_one_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy_dev, const uint8_t* g1_inf_dev,
+                                       const uint64_t* g2_xy_dev, const uint8_t* g2_inf_dev, size_t n, size_t group, uint8_t* ok_dev) {
+  if (!g1_xy_dev || !g1_inf_dev || !g2_xy_dev || !g2_inf_dev || !ok_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pairing_vtbl(curve)->product_is_one(ctx, g1_xy_dev, g1_inf_dev, g2_xy_dev, g2_inf_dev, n, group, ok_dev); });
+}
+int32_t zkp_pairing(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                    const uint8_t* g2_inf, size_t n, uint64_t* gt_out) {
+  if (!g1_xy || !g1_inf || !g2_xy || !g2_inf || !gt_out) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pairing_vtbl(curve)->pairing_host(ctx, g1_xy, g1_inf, g2_xy, g2_inf, n, gt_out); });
+}
+int32_t zkp_pairing_check(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                          const uint8_t* g2_inf, size_t n, size_t group, uint8_t* ok_out) {
+  if (!g1_xy || !g1_inf || !g2_xy || !g2_inf || !ok_out) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { pairing_vtbl(curve)->check_host(ctx, g1_xy, g1_inf, g2_xy, g2_inf, n, group, ok_out); });
 }
 int32_t zkp_hash_params_create(zkp_ctx* ctx, zkp_curve_t curve, const zkp_hash_desc* desc, zkp_hash_params** out) {
   if (!desc || !out) return ZKP_ERR_BAD_ARG;

@@ -168,6 +168,8 @@ struct zkp_ctx {
   std::map<std::pair<int, int>, zkp::NttTables> ntt_tables;   // (curve, log_n)
   zkp::DevBuf ntt_io, poly_tmp, poly_consts, spmv_list;
   zkp::DevBuf g1_ntt_tw;           // zkp_g1_ntt_dev: the n / 2 twiddles and 1 / n of the transform in flight (g1_ntt.hip)
+  zkp::DevBuf pairing_tmp;         // zkp_pairing_*: the Miller parts of the groups that span workgroups, then the m products (pairing.hip)
+  zkp::DevBuf pairing_io;          // zkp_pairing / zkp_pairing_check: the staged host points and results
   // MSM scratch
   zkp::DevBuf msm_scalars, msm_misc, var_bases;
   uint32_t* pinned = nullptr;      // pinned host landing zone for batched MSM results

@@ -5,6 +5,8 @@ Mirrors /root/reference/groth16/src/lib.rs:39-91 (`Parameters`, `Proof`, `create
 Setup (`generate_parameters`, /root/reference/groth16/src/generator.rs:135-286) is NOT part of the hot path;
 it is provided with an explicit trapdoor so that synthetic keys of 2^20+ constraints can be produced on the
 GPU (zkp_fixed_base_mul_*) for the parity tests and the benchmark.
+The verifier (/root/reference/groth16/src/verifier.rs:8-44: `prepare_verifying_key`, `verify_proof`) runs on the device's pairings
+(ckb_zkp_amd/pairing.py); `verify_proofs_batch` checks many proofs with one final exponentiation.
 """
 from __future__ import annotations
 
@@ -576,3 +578,122 @@ def create_random_proof(pk: ProvingKey, circuit, rng=None) -> Proof:
 def create_proof_no_zk(pk: ProvingKey, circuit) -> Proof:
     """prover.rs:113-122"""
     return create_proof(pk, circuit, 0, 0)
+
+
+# ------------------------------------------------------------------------------------------------ verifier
+@dataclass
+class VerifyKey:
+    """groth16/src/lib.rs:59-66: the verifier's view of `Parameters`, in ABI layout (Montgomery limbs + identity flags)."""
+    curve: CurveParams
+    alpha_g1: np.ndarray
+    beta_g2: np.ndarray
+    gamma_g2: np.ndarray
+    delta_g2: np.ndarray
+    gamma_abc_g1: tuple            # (xy, inf)
+
+    @classmethod
+    def of(cls, params: Parameters) -> "VerifyKey":
+        return cls(params.curve, params.alpha_g1, params.beta_g2, params.gamma_g2, params.delta_g2, params.gamma_abc_g1)
+
+
+@dataclass
+class PreparedVerifyingKey:
+    """groth16/src/lib.rs:68-77: e(alpha, beta) as the ABI's Fq12 words (the library's GT value: the reduced pairing raised to
+    pairing.GT_POWER), -gamma and -delta as canonical G2 points."""
+    vk: VerifyKey
+    alpha_g1_beta_g2: np.ndarray
+    gamma_g2_neg: tuple
+    delta_g2_neg: tuple
+
+
+def _neg_g2(p, c: CurveParams):
+    return None if p is None else (p[0], ((-p[1][0]) % c.q, (-p[1][1]) % c.q))
+
+
+def prepare_verifying_key(ctx: Context, params) -> PreparedVerifyingKey:
+    """verifier.rs:8-16; params: Parameters or VerifyKey.  One pairing on the device."""
+    from . import pairing as pr
+    vk = params if isinstance(params, VerifyKey) else VerifyKey.of(params)
+    c = vk.curve
+    zero = np.zeros(1, dtype=np.uint8)
+    ab = ctx.pairing(c, vk.alpha_g1.reshape(1, -1), zero, vk.beta_g2.reshape(1, -1), zero)[0]
+    gamma = g2_from_mont(vk.gamma_g2.reshape(1, -1), None, c)[0]
+    delta = g2_from_mont(vk.delta_g2.reshape(1, -1), None, c)[0]
+    assert pr.GT_POWER[c.name] == ctx.pairing_info(c)["gt_power"]
+    return PreparedVerifyingKey(vk, ab, _neg_g2(gamma, c), _neg_g2(delta, c))
+
+
+def _msm_g1_affine(ctx: Context, c: CurveParams, xy: np.ndarray, inf, scalars) -> tuple:
+    """sum_i [s_i] P_i through the small variable-base MSM -> affine canonical point or None"""
+    xyz = ctx.msm_var(c, 1, xy, inf, fr_canonical(scalars, c))
+    a, is_inf = ctx.into_affine(c, 1, xyz)
+    return g1_from_mont(a, [is_inf], c)[0]
+
+
+def verify_proof(ctx: Context, pvk: PreparedVerifyingKey, proof: Proof, public_inputs) -> bool:
+    """verifier.rs:18-44: g_ic = gamma_abc[0] + sum x_i gamma_abc[i + 1] (the small MSM), then
+    final_exp(miller(A, B) miller(g_ic, -gamma) miller(C, -delta)) == e(alpha, beta): three pairs in one Miller launch, one final
+    exponentiation."""
+    from . import pairing as pr
+    from .r1cs import SynthesisError
+    vk, c = pvk.vk, pvk.vk.curve
+    abc_xy, abc_inf = vk.gamma_abc_g1
+    if len(public_inputs) + 1 != len(abc_xy):
+        raise SynthesisError("MalformedVerifyingKey")
+    if public_inputs:
+        g_ic = _msm_g1_affine(ctx, c, abc_xy, abc_inf, [1] + [x % c.r for x in public_inputs])
+    else:
+        g_ic = g1_from_mont(abc_xy[:1], abc_inf[:1], c)[0]
+    g1, i1, g2, i2 = pr._points(c, [proof.a, g_ic, proof.c], [proof.b, pvk.gamma_g2_neg, pvk.delta_g2_neg])
+    gt = pr.miller_products_mont(ctx, c, g1, i1, g2, i2, 3, final_exp=True)[0]
+    return bool(np.array_equal(gt, pvk.alpha_g1_beta_g2))
+
+
+def batch_coefficients(curve, n: int, seed: int, bits: int = 128) -> list:
+    """n non-zero `bits`-bit coefficients for verify_proofs_batch from a seeded generator (a verifier draws them after it has seen
+    the proofs; a test fixes the seed)."""
+    import random
+    rng = random.Random(seed)
+    return [rng.randrange(1, 1 << bits) % get_curve(curve).r or 1 for _ in range(n)]
+
+
+def verify_proofs_batch(ctx: Context, pvk: PreparedVerifyingKey, proofs, inputs_list, coeffs) -> bool:
+    """n proofs under the random linear combination rho_i (coeffs, supplied by the caller; batch_coefficients draws them):
+
+        prod_i e(rho_i A_i, B_i) * e(sum_i rho_i g_ic_i, -gamma) * e(sum_i rho_i C_i, -delta) * e(-(sum_i rho_i) alpha, beta) == 1
+
+    n + 3 pairs in ONE Miller launch and ONE final exponentiation.  The G1 work goes through the existing entries: the rho_i A_i and
+    -(sum rho) alpha are one per-lane scaling, sum rho_i C_i and sum rho_i g_ic_i (= the MSM of gamma_abc by the rho-weighted input
+    sums) are small MSMs.  True iff every proof verifies, up to the soundness error of the combination (about n / 2^bits for
+    independent random rho_i; all rho_i = 1 is sound only against proofs made without knowledge of each other).
+    This check is NOT in the reference's lib.rs (it verifies one proof at a time), as asvc.prove_all is not."""
+    from . import pairing as pr
+    from .r1cs import SynthesisError
+    vk, c = pvk.vk, pvk.vk.curve
+    r = c.r
+    n = len(proofs)
+    abc_xy, abc_inf = vk.gamma_abc_g1
+    ni = len(abc_xy)
+    if n < 1 or len(inputs_list) != n or len(coeffs) != n:
+        raise ValueError("one input list and one coefficient per proof, at least one proof")
+    if any(len(x) + 1 != ni for x in inputs_list):
+        raise SynthesisError("MalformedVerifyingKey")
+    rho = [k % r for k in coeffs]
+    total = sum(rho) % r
+    # rho_i A_i and -(sum rho) alpha: one scaling launch
+    a_xy, a_inf = g1_to_mont([p.a for p in proofs], c)
+    sc_xy = np.concatenate([a_xy, vk.alpha_g1.reshape(1, -1)])
+    sc_inf = np.concatenate([a_inf, np.zeros(1, dtype=np.uint8)])
+    s_xy, s_inf = ctx.g1_scale_vec(c, sc_xy, sc_inf, fr_to_mont(rho + [(-total) % r], c).reshape(n + 1, 4))
+    # sum rho_i g_ic_i: gamma_abc weighted by sum_i rho_i x_ij (x_i0 = 1)
+    w = [total] + [sum(rho[i] * inputs_list[i][j] for i in range(n)) % r for j in range(ni - 1)]
+    g_ic = _msm_g1_affine(ctx, c, abc_xy, abc_inf, w)
+    c_xy, c_inf = g1_to_mont([p.c for p in proofs], c)
+    c_sum = _msm_g1_affine(ctx, c, c_xy, c_inf, rho)
+    t_xy, t_inf = g1_to_mont([g_ic, c_sum], c)
+    b_xy, b_inf = g2_to_mont([p.b for p in proofs] + [pvk.gamma_g2_neg, pvk.delta_g2_neg], c)
+    g1 = np.concatenate([s_xy[:n], t_xy, s_xy[n:]])
+    i1 = np.concatenate([s_inf[:n], t_inf, s_inf[n:]])
+    g2 = np.concatenate([b_xy, vk.beta_g2.reshape(1, -1)])
+    i2 = np.concatenate([b_inf, np.zeros(1, dtype=np.uint8)])
+    return bool(ctx.pairing_check(c, g1, i1, g2, i2, n + 3)[0])

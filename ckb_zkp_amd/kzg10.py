@@ -5,6 +5,7 @@
 kzg10.rs:27-31); `commit` and `open` are the prover-side hot path: coefficient vectors live in HBM, the witness
 polynomial p/(X - z) and the evaluations are computed on the device, and the MSMs run against the resident powers
 with `offset = number of leading zero coefficients` exactly as `skip_leading_zeros_and_convert_to_bigints` does.
+`check` (kzg10.rs:158-173) and `batch_check` run on the device's pairings (ckb_zkp_amd/pairing.py).
 """
 from __future__ import annotations
 
@@ -137,3 +138,79 @@ def open(ctx: Context, ck: CommitterKey, coeffs_mont: np.ndarray, point: int, bl
         rand_v = codec.fr_from_mont(ev.reshape(1, 4), c)[0]
     xy, inf = ctx.into_affine(c, 1, w)
     return codec.g1_from_mont(xy, [inf], c)[0], rand_v
+
+
+# ------------------------------------------------------------------------------------------------ verifier
+def _neg_g1(p, c):
+    return None if p is None else (p[0], (-p[1]) % c.q)
+
+
+def _jacobian_rows_to_affine(c, group: int, xyz: np.ndarray) -> list:
+    """(m, 3 w) Montgomery Jacobian points -> affine canonical integers (None = identity) on the host, in Python integers: the
+    2 m results of a batch are host data anyway, and one zkp_g*_into_affine call per point would be 2 m synchronous device calls."""
+    q = c.q
+    out = []
+    for row in np.asarray(xyz, dtype=np.uint64).reshape(len(xyz), -1):
+        v = codec._fq_list(row, c)
+        if group == 1:
+            x, y, z = v
+            if z == 0:
+                out.append(None)
+                continue
+            zi = pow(z, -1, q)
+            out.append((x * zi * zi % q, y * zi * zi * zi % q))
+        else:
+            mul = lambda a, b: ((a[0] * b[0] - a[1] * b[1]) % q, (a[0] * b[1] + a[1] * b[0]) % q)   # noqa: E731
+            x, y, z = (v[0], v[1]), (v[2], v[3]), (v[4], v[5])
+            if z == (0, 0):
+                out.append(None)
+                continue
+            ni = pow((z[0] * z[0] + z[1] * z[1]) % q, -1, q)
+            zi = (z[0] * ni % q, (-z[1]) * ni % q)
+            zi2 = mul(zi, zi)
+            out.append((mul(x, zi2), mul(y, mul(zi2, zi))))
+    return out
+
+
+def _check_pairs(ctx: Context, ck: CommitterKey, openings):
+    """per opening (comm, point, value, (w, rand_v)): u = comm - value g - rand_v gamma_g and v = beta_h - point h, as two batches of
+    small MSMs; the pairs (u, h), (-w, v)"""
+    c = ck.curve
+    r = c.r
+    h, beta_h = ck.vk_g2
+    g = codec.g1_from_mont(ck.host_g[0][:1], ck.host_g[1][:1], c)[0]
+    gamma_g = codec.g1_from_mont(ck.host_gamma_g[0][:1], ck.host_gamma_g[1][:1], c)[0]
+    xs1, is1, ss1, xs2, is2, ss2 = [], [], [], [], [], []
+    for comm, point, value, (w, rand_v) in openings:
+        xy, inf = codec.g1_to_mont([comm, g, gamma_g], c)
+        xs1.append(xy)
+        is1.append(inf)
+        ss1.append(codec.fr_canonical([1, (-value) % r, (-(rand_v or 0)) % r], c))
+        xy, inf = codec.g2_to_mont([beta_h, h], c)
+        xs2.append(xy)
+        is2.append(inf)
+        ss2.append(codec.fr_canonical([1, (-point) % r], c))
+    u = ctx.msm_var_batch(c, 1, xs1, is1, ss1)
+    v = ctx.msm_var_batch(c, 2, xs2, is2, ss2)
+    ua, va = _jacobian_rows_to_affine(c, 1, u), _jacobian_rows_to_affine(c, 2, v)
+    g1_pts, g2_pts = [], []
+    for k, (_, _, _, (w, _)) in enumerate(openings):
+        g1_pts += [ua[k], _neg_g1(w, c)]
+        g2_pts += [h, va[k]]
+    return g1_pts, g2_pts
+
+
+def check(ctx: Context, ck: CommitterKey, comm, point: int, value: int, proof) -> bool:
+    """KZG10::check (kzg10.rs:158-173): e(comm - value g - rand_v gamma_g, h) == e(w, beta_h - point h), as
+    e(u, h) e(-w, v) == 1: two pairs, one final exponentiation.  proof: (w, rand_v) as `open` returns it; ck carries the
+    VerifierKey's parts (g, gamma_g, h, beta_h)."""
+    return batch_check(ctx, ck, [(comm, point, value, proof)])[0]
+
+
+def batch_check(ctx: Context, ck: CommitterKey, openings) -> list:
+    """`check` for many openings [(comm, point, value, proof)] as m groups of two pairs: one Miller launch, one final exponentiation
+    launch, one verdict per opening (so a bad opening is located by its index).  Before the pairing launches: the u and v of all
+    openings are two batched small-MSM calls (one upload per opening's points: host data), made affine on the host."""
+    from . import pairing as pr
+    g1_pts, g2_pts = _check_pairs(ctx, ck, list(openings))
+    return pr.product_is_one(ctx, ck.curve, g1_pts, g2_pts, group=2)

@@ -61,7 +61,9 @@ const char* zkp_status_string(int32_t status);
  * (matrix polynomial commitments over a resident Pedersen key),
  * then zkp_g1_scale_vec_dev / zkp_g1_ntt_dev (per-lane scalar multiplication and the transform over G1 points),
  * then zkp_hash_params_create / zkp_hash_params_free / zkp_hash_params_info / zkp_fr_hash_blocks_dev / zkp_fr_hash_chain_dev /
- * zkp_fr_mimc_trace_dev / zkp_fr_merkle_tree_dev / zkp_fr_merkle_paths_dev (MiMC, Poseidon and Rescue hashing, CBMT Merkle trees).
+ * zkp_fr_mimc_trace_dev / zkp_fr_merkle_tree_dev / zkp_fr_merkle_paths_dev (MiMC, Poseidon and Rescue hashing, CBMT Merkle trees),
+ * then zkp_pairing_info / zkp_pairing_miller_dev / zkp_pairing_final_exp_dev / zkp_pairing_product_is_one_dev / zkp_pairing /
+ * zkp_pairing_check (optimal-ate pairings: the Groth16 and KZG10 verifiers).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -646,6 +648,49 @@ int32_t zkp_fr_merkle_tree_dev(zkp_ctx* ctx, const zkp_hash_params* params, int3
 #define ZKP_MERKLE_BAD_LEAF 4294967295u
 int32_t zkp_fr_merkle_paths_dev(zkp_ctx* ctx, const uint64_t* nodes_dev, size_t n, const uint32_t* leaf_idx_dev, size_t q,
                                 uint64_t* out_dev, size_t stride, uint32_t* len_dev);
+/* Optimal-ate pairings (later in 0.7.1, detected by symbol): products of Miller functions and the final exponentiation on BN254 and
+ * BLS12-381, the primitive of groth16::verify_proof (groth16/src/verifier.rs:8-44), KZG10::check (marlin/src/pc/kzg10.rs:158-173)
+ * and the aSVC checks.  n pairs (P_i, Q_i) form m = n / group groups of `group` consecutive pairs; a group's value is the product of
+ * its pairs' Miller functions, and checking it costs ONE final exponentiation.
+ *
+ * Points: the layouts of zkp_msm_g1_var / zkp_msm_g2_var, affine Montgomery words (G1: x, y; G2: x.c0, x.c1, y.c0, y.c1) plus one
+ * identity flag byte per point; both flag arrays are required.  A pair with a flagged point contributes 1.  The entries do NOT test
+ * curve or subgroup membership: callers use zkp_g1_subgroup_check / zkp_g2_subgroup_check (a point off the curve gives a value
+ * without meaning, never a fault).
+ * An Fq12 is 12 Fq, Montgomery, in ark's tower order c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2, each an Fq2 (c0, c1), over
+ * Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - xi), xi = 9 + u (BN254) / 1 + u (BLS12-381): c_j.c_i is the coefficient of
+ * w^(2 i + j).  48 / 72 u64 words.  Every element written is fully reduced (< q): equality of GT values is equality of words.
+ * The final exponentiation returns f^(k (q^12 - 1) / r) for a per-curve constant k coprime to r, fixed at compile time: k = 1 on
+ * BN254, k = 3 on BLS12-381.  A pairing value is therefore e(P, Q)^k: bilinear, non-degenerate, comparable with other values of this
+ * library only.  An input of 0 gives 0 (Fq's inversion maps 0 to 0); the Miller function of valid points is never 0.
+ *
+ * zkp_pairing_info: info[0] k, [1] u64 words per Fq12, [2] pairs per workgroup, [3] ZKP_PAIRING_MAX_N, [4] LDS bytes of the Miller
+ * kernel, [5..7] 0.  Needs no device.
+ * zkp_pairing_miller_dev: out[j] = the product over the pairs of group j of the optimal-ate Miller function, m Fq12; defined up to
+ * factors that the final exponentiation removes.  One pair per lane; the pairs of a group are multiplied in a tree over the wave in
+ * LDS, and a second launch joins the parts of a group that spans workgroups.  Two launches; one, and no scratch, when `group`
+ * divides 64 (no group spans workgroups).
+ * zkp_pairing_final_exp_dev: out[e] = final_exp(f[e]) for e < m, one element per lane, one launch.  out_gt_dev may be f12_dev itself
+ * (in place); any other overlap is refused.
+ * zkp_pairing_product_is_one_dev: both steps, then ok_dev[j] = 1 iff group j's GT value is one, else 0; m bytes.  Four launches (three when `group` divides 64).
+ * The three *_dev entries run on the context's current stream and only launch; intermediate values live in the context's grow-only
+ * scratch.
+ * zkp_pairing: HOST pointers; gt_out[i] = e(P_i, Q_i)^k for i < n, n Fq12.  zkp_pairing_check: HOST pointers; ok_out[j] as above.
+ * Both stage, run and synchronise.
+ * ZKP_ERR_BAD_ARG, before anything runs and with every output untouched: a NULL pointer, a point or Fq12 pointer in device memory
+ * that is not 16-byte aligned, n, m or group == 0, n not a multiple of group, n or m above ZKP_PAIRING_MAX_N, an unknown curve, an
+ * output that overlaps an input (but for the in-place case above). */
+#define ZKP_PAIRING_MAX_N 1048576
+int32_t zkp_pairing_info(zkp_curve_t curve, uint64_t* info);
+int32_t zkp_pairing_miller_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy_dev, const uint8_t* g1_inf_dev,
+                               const uint64_t* g2_xy_dev, const uint8_t* g2_inf_dev, size_t n, size_t group, uint64_t* out_f12_dev);
+int32_t zkp_pairing_final_exp_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* f12_dev, size_t m, uint64_t* out_gt_dev);
+int32_t zkp_pairing_product_is_one_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy_dev, const uint8_t* g1_inf_dev,
+                                       const uint64_t* g2_xy_dev, const uint8_t* g2_inf_dev, size_t n, size_t group, uint8_t* ok_dev);
+int32_t zkp_pairing(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                    const uint8_t* g2_inf, size_t n, uint64_t* gt_out);
+int32_t zkp_pairing_check(zkp_ctx* ctx, zkp_curve_t curve, const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy,
+                          const uint8_t* g2_inf, size_t n, size_t group, uint8_t* ok_out);
 /* PLONK prover rounds 2 and 3 (later in 0.7.1, detected by symbol): the table work of AHPForPLONK::prover_second_round /
  * prover_third_round (plonk/src/ahp/prover.rs:135-216), every table kept on the device.  The transforms around them are
  * zkp_ntt_dev, the commitments zkp_msm_g1_mont_dev; the transcript stays with the caller.  Vectors: Fr, Montgomery, canonical,
