@@ -36,6 +36,8 @@ UNITS = [("ntt.hip", "ntt.o", ["-DZKP_INLINE_MUL"]),
          ("msm.hip", "msm.o", []),
          ("groth16.hip", "groth16.o", ["-DZKP_INLINE_MUL"]),
          ("groth16_key.hip", "groth16_key.o", ["-DZKP_INLINE_MUL"]),   # the Groth16 key: upload phase by phase, evaluation-form transforms + C fold, info, release
+         ("groth16_multi.hip", "groth16_multi.o", []),                 # the multi-device Groth16 prover, phase by phase: host code only
+         ("rccl_gather.hip", "rccl_gather.o", []),                     # RCCL all-gather resolved at run time, brought up under a watchdog: host code only
          ("capi.hip", "capi.o", []),
          ("bench_kern.hip", "bench_kern.o", ["-DZKP_INLINE_MUL"] + UNROLL),
          ("fs_rng.cpp", "fs_rng.o", []),

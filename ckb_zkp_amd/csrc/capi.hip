@@ -34,16 +34,14 @@ int32_t guarded(zkp_ctx* ctx, Fn&& fn) {
     ZKP_HIP(hipSetDevice(ctx->device));
     fn();
     return ZKP_OK;
-  } catch (const StatusError& e) {
-    return e.status;
-  } catch (const HipError& e) {
-    ctx->last_error = std::string(e.what) + ": " + hipGetErrorString(e.e);
-    fprintf(stderr, "[zkp_accel] HIP error %s at line %d: %s\n", hipGetErrorString(e.e), e.line, e.what);
-    return e.e == hipErrorOutOfMemory ? ZKP_ERR_OOM : ZKP_ERR_DEVICE;
-  } catch (const std::bad_alloc&) {
-    return ZKP_ERR_OOM;
   } catch (...) {
-    return ZKP_ERR_DEVICE;
+    HipError e{hipSuccess, nullptr, 0};
+    const int32_t status = status_of_current_exception(&e);
+    if (e.what) {
+      ctx->last_error = std::string(e.what) + ": " + hipGetErrorString(e.e);
+      fprintf(stderr, "[zkp_accel] HIP error %s at line %d: %s\n", hipGetErrorString(e.e), e.line, e.what);
+    }
+    return status;
   }
 }
 

@@ -26,7 +26,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
@@ -102,53 +101,67 @@ __global__ void scalar_tail_kernel(uint32_t* tail, const uint32_t* rs, size_t ta
   (r * s).neg().store(tail + 24);
 }
 
-// z_dev: nz Fr (device).  Leaves h (N Fr, Montgomery) in pk->abc[0..N)
-// coeffs: h in coefficient form wanted (zkp_groth16_witness_map; the prover of a coefficient-form key); false with an evaluation-form
-// key: the pointwise values v on the coset, the scalars of its H MSM
-template <class P>
-static uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, bool coeffs = true, int g = 0, int G = 1) {
-  // g, G: proof g of a fused group of G (ProofJob) works in the g-th of G abc regions of the lane
+// ---- the witness map in the pieces both provers compose (groth16_pk.hpp), each on the current stream of ctx.  a | b | c are the
+// three N-element thirds of one abc region of a lane; chain k = 0 / 1 / 2 is A z / B z / C z and works in the k-th of them.
+void witness_eval(zkp_ctx* ctx, const zkp_groth16_pk* pk, const uint32_t* z_dev, int k, uint32_t* out) {
   const uint32_t N = (uint32_t)pk->N;
-  uint32_t* a = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8 * (size_t)G) + (size_t)g * 3 * pk->N * 8;
+  with_fr(pk->curve, [&](auto P) {
+    hipLaunchKernelGGL(csr_eval_kernel<decltype(P)>, dim3((N + 255) / 256), dim3(256), 0, ctx->cur->stream, pk->m[k].row_ptr,
+                       pk->m[k].col, pk->m[k].coeff, z_dev, pk->num_constraints, N, pk->num_inputs, k == 0 ? 1 : 0, out);
+  });
+}
+
+// ifft -> coset_fft as one chain of passes (1/N folded into the coset table, no odd-pass copies); falls back to the two
+// separate transforms above the full-table domain limit
+void witness_transform(zkp_ctx* ctx, const zkp_groth16_pk* pk, uint32_t* buf) {
+  if (ntt_ifft_coset_fft(ctx, pk->curve, buf, pk->log_n)) return;
+  ntt_run(ctx, pk->curve, buf, pk->log_n, ZKP_NTT_IFFT);
+  ntt_run(ctx, pk->curve, buf, pk->log_n, ZKP_NTT_COSET_FFT);
+}
+
+// (a, b, c) on the coset -> h, which it returns (it lands in a or b).  coeffs: h in coefficient form wanted
+// (zkp_groth16_witness_map; the prover of a coefficient-form key); false with an evaluation-form key: the pointwise values v on the
+// coset, the scalars of its H MSM
+uint32_t* witness_finish(zkp_ctx* ctx, zkp_groth16_pk* pk, uint32_t* a, bool coeffs) {
+  const uint32_t N = (uint32_t)pk->N;
   uint32_t* b = a + pk->N * 8;
   uint32_t* c = b + pk->N * 8;
-  uint32_t* bufs[3] = {a, b, c};
+  const uint32_t* zinv = pk->consts.as<uint32_t>(64);
   hipStream_t st = ctx->cur->stream;
+  uint32_t* h = a;
+  with_fr(pk->curve, [&](auto P) {
+    using FrP = decltype(P);
+    if (!coeffs && pk->c_folded) {
+      hipLaunchKernelGGL(qap_pointwise_ab_kernel<FrP>, dim3((N + 255) / 256), dim3(256), 0, st, a, b, zinv, N);
+    } else if (!coeffs) {
+      hipLaunchKernelGGL(qap_pointwise_kernel<FrP>, dim3((N + 255) / 256), dim3(256), 0, st, a, b, c, zinv, N);
+    } else if (uint32_t* hq = ntt_qap_coset_ifft(ctx, pk->curve, a, b, c, zinv, pk->log_n)) {
+      h = hq;                                            // (a*b - c) / Z(g) fused into the first pass of coset_ifft
+    } else {
+      hipLaunchKernelGGL(qap_pointwise_kernel<FrP>, dim3((N + 255) / 256), dim3(256), 0, st, a, b, c, zinv, N);
+      ntt_run(ctx, pk->curve, a, pk->log_n, ZKP_NTT_COSET_IFFT);
+    }
+  });
+  ZKP_HIP(hipGetLastError());
+  return h;
+}
+
+// z_dev: nz Fr (device).  Leaves h (N Fr, Montgomery) in the lane's abc and returns it; coeffs as for witness_finish.
+// g, G: proof g of a fused group of G (ProofJob) works in the g-th of G abc regions of the lane
+uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, bool coeffs, int g, int G) {
+  uint32_t* a = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8 * (size_t)G) + (size_t)g * 3 * pk->N * 8;
+  uint32_t* bufs[3] = {a, a + pk->N * 8, a + 2 * pk->N * 8};
   const int nchain = (!coeffs && pk->c_folded) ? 2 : 3;            // C folded into the L query: no C z, no c chain
-  for (int k = 0; k < nchain; k++)
-    hipLaunchKernelGGL(csr_eval_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, st, pk->m[k].row_ptr, pk->m[k].col,
-                       pk->m[k].coeff, z_dev, pk->num_constraints, N, pk->num_inputs, k == 0 ? 1 : 0, bufs[k]);
+  for (int k = 0; k < nchain; k++) witness_eval(ctx, pk, z_dev, k, bufs[k]);
   // One launch for a, b, c (grid.y = 3) shortens the witness map in isolation (1.49 -> 1.35 ms at 2^20) but its 3x larger
   // launches delay the MSM streams of the other lane: 79 vs 85 proofs/s pipelined.  Off unless ZKP_NTT_BATCH=1.
   if (ctx->tune.ntt_batch) {
     ntt_run_batch(ctx, pk->curve, bufs, nchain, pk->log_n, ZKP_NTT_IFFT);
     ntt_run_batch(ctx, pk->curve, bufs, nchain, pk->log_n, ZKP_NTT_COSET_FFT);
   } else {
-    for (int k = 0; k < nchain; k++) {
-      // ifft -> coset_fft as one chain of passes (1/N folded into the coset table, no odd-pass copies); falls back to the two
-      // separate transforms above the full-table domain limit
-      if (!ntt_ifft_coset_fft(ctx, pk->curve, bufs[k], pk->log_n)) {
-        ntt_run(ctx, pk->curve, bufs[k], pk->log_n, ZKP_NTT_IFFT);
-        ntt_run(ctx, pk->curve, bufs[k], pk->log_n, ZKP_NTT_COSET_FFT);
-      }
-    }
+    for (int k = 0; k < nchain; k++) witness_transform(ctx, pk, bufs[k]);
   }
-  if (!coeffs) {
-    if (pk->c_folded) hipLaunchKernelGGL(qap_pointwise_ab_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, st, a, b, pk->consts.as<uint32_t>(64), N);
-    else hipLaunchKernelGGL(qap_pointwise_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, st, a, b, c, pk->consts.as<uint32_t>(64), N);
-    ZKP_HIP(hipGetLastError());
-    return a;
-  }
-  // (a*b - c) / Z(g) fused into the first pass of coset_ifft; h lands in a or b
-  if (uint32_t* hq = ntt_qap_coset_ifft(ctx, pk->curve, a, b, c, pk->consts.as<uint32_t>(64), pk->log_n)) {
-    ZKP_HIP(hipGetLastError());
-    return hq;
-  }
-  hipLaunchKernelGGL(qap_pointwise_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, st, a, b, c,
-                     pk->consts.as<uint32_t>(64), N);
-  ntt_run(ctx, pk->curve, a, pk->log_n, ZKP_NTT_COSET_IFFT);
-  ZKP_HIP(hipGetLastError());
-  return a;
+  return witness_finish(ctx, pk, a, coeffs);
 }
 
 void groth16_witness_map(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, uint64_t* h, bool on_device) {
@@ -158,7 +171,7 @@ void groth16_witness_map(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint64_t* z, ui
     ZKP_HIP(hipMemcpyAsync(s, z, pk->nz * 32, hipMemcpyHostToDevice, ctx->cur->stream));
     zd = s;
   }
-  uint32_t* hd = with_fr(pk->curve, [&](auto P) { return witness_map_dev<decltype(P)>(ctx, pk, zd); });
+  uint32_t* hd = witness_map_dev(ctx, pk, zd);
   ZKP_HIP(hipMemcpyAsync(h, hd, pk->N * 32, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->cur->stream));
   if (!on_device) ZKP_HIP(hipStreamSynchronize(ctx->cur->stream));
 }
@@ -221,6 +234,45 @@ struct AssembleBuf {
 };
 static_assert(MAX_PROOF_WORDS <= AssembleBuf::PROOF_WORDS && AssembleBuf::PROOF_WORDS + FLAG_STEP <= AssembleBuf::TAIL_WORDS,
               "proof and flags fit the tail of the carve-up");
+
+// ---- the steps of a proof on one lane that ProofRun and the multi-device prover's legs share (groth16_pk.hpp)
+// One proof's z, r, s into its S vector (nz + 4 scalars) and its [r, s] pair.  The copies and the tails are two calls because a
+// captured graph holds the launch but not the copies.
+void proof_copy_inputs(hipStream_t st, const zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
+                       const uint64_t* s, uint32_t* S, uint32_t* rs) {
+  ZKP_HIP(hipMemcpyAsync(S, z, pk->nz * 32, z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
+  ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
+}
+// the tails [1, r, s, -r*s] of the G consecutive S vectors of a group, one launch
+void proof_scalar_tails(hipStream_t st, const zkp_groth16_pk* pk, uint32_t* S, const uint32_t* rs, int G) {
+  with_fr(pk->curve, [&](auto P) {
+    hipLaunchKernelGGL(scalar_tail_kernel<decltype(P)>, dim3(G), dim3(64), 0, st, S + pk->nz * 8, rs, (pk->nz + 4) * 8);
+  });
+}
+// The request of query idx (0..4: A, B1, B2, H, L) over this key's slice of it: scalars = the witness map's output for H, S for the
+// others; the sum goes to slot idx of res.  Workspace, sort sharing and the rest stay with the caller.
+MsmJob proof_query_job(const zkp_groth16_pk* pk, int idx, const uint32_t* scalars, char* res, size_t slot) {
+  const uint64_t handles[5] = {pk->hA, pk->hB1, pk->hB2, pk->hH, pk->hL};
+  MsmJob m;
+  m.handle = handles[idx];
+  m.scalars_dev = reinterpret_cast<const uint64_t*>(scalars) + 4 * pk->q_lo[idx];
+  m.n = pk->q_n[idx];
+  m.montgomery = true;
+  m.out_dev_xyzz = res + idx * slot;
+  return m;
+}
+// the lane's workspace streams wait for what its main stream holds so far (S is complete) / the main stream waits for them
+void lane_fork(zkp_lane* lane) {
+  ZKP_HIP(hipEventRecord(lane->ev_fork, lane->stream));
+  for (int w = 1; w < zkp_ctx::N_WS; w++) ZKP_HIP(hipStreamWaitEvent(lane->ws[w].stream, lane->ev_fork, 0));
+}
+void lane_join(zkp_lane* lane) {
+  for (int w = 1; w < zkp_ctx::N_WS; w++) {
+    ZKP_HIP(hipEventRecord(lane->ws[w].done, lane->ws[w].stream));
+    ZKP_HIP(hipStreamWaitEvent(lane->stream, lane->ws[w].done, 0));
+  }
+}
 
 // One proof, or one fused group of proofs, to enqueue on the current lane (ctx->cur); filled by field assignment.
 // G > 1: a FUSED GROUP of G proofs over the same key in the kernel chain of one.  The
@@ -336,22 +388,16 @@ struct ProofRun {
 
   // z, r, s into the lane's buffers: all that runs in front of a graph launch
   void copy_inputs() {
-    const hipMemcpyKind z_kind = job.z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    for (int g = 0; g < G; g++) {
-      ZKP_HIP(hipMemcpyAsync(S + g * s_stride * 8, job.z[g], pk->nz * 32, z_kind, st));
-      ZKP_HIP(hipMemcpyAsync(buf.rs + RS_STEP * g, job.r + 4 * g, 32, hipMemcpyHostToDevice, st));
-      ZKP_HIP(hipMemcpyAsync(buf.rs + RS_STEP * g + 8, job.s + 4 * g, 32, hipMemcpyHostToDevice, st));
-    }
+    for (int g = 0; g < G; g++)
+      proof_copy_inputs(st, pk, job.z[g], job.z_on_device, job.r + 4 * g, job.s + 4 * g, S + g * s_stride * 8, buf.rs + RS_STEP * g);
   }
 
   // everything behind the inputs: what a hipGraph captures
   void enqueue() {
-    with_fr(pk->curve, [&](auto P) {
-      hipLaunchKernelGGL(scalar_tail_kernel<decltype(P)>, dim3(G), dim3(64), 0, st, S + pk->nz * 8, buf.rs, s_stride * 8);
-    });
+    proof_scalar_tails(st, pk, S, buf.rs, G);
     ctx->tl_tag.clear();
     ctx->mark(st, "start");
-    if (fan) fork();
+    if (fan) lane_fork(lane);
     // The witness map heads the longest chain of a proof (witness map -> H MSM -> assembly): its launches go out FIRST, before
     // the ~150 launches of the four other MSMs (0.5 ms of host time): single-proof latency 10.1 -> 9.65 ms (ZKP_WM_FIRST=0: after
     // them, as in round 1).  Making the other MSMs' accumulate kernels wait for it — a kernel timeline shows machine-filling
@@ -372,7 +418,7 @@ struct ProofRun {
     // chained: on top of L's buckets (workspace 1): result slot 3 = h_acc + l', slot 4 = identity
     msm(3, 0, -1, -1, false, chained ? 1 : -1);        // prover.rs:186-187 (min(len) truncation in q_n)
     if (!l_done) msm(4, 0);                            // prover.rs:189-190
-    if (fan) join();
+    if (fan) lane_join(lane);
     if (job.partial_out) {
       emit_partials();
     } else {
@@ -382,27 +428,14 @@ struct ProofRun {
     timer.finish();
   }
 
-  void fork() {
-    ZKP_HIP(hipEventRecord(lane->ev_fork, st));                       // S is complete
-    for (int w = 1; w < zkp_ctx::N_WS; w++) ZKP_HIP(hipStreamWaitEvent(lane->ws[w].stream, lane->ev_fork, 0));
-  }
-  void join() {
-    for (int w = 1; w < zkp_ctx::N_WS; w++) {
-      ZKP_HIP(hipEventRecord(lane->ws[w].done, lane->ws[w].stream));
-      ZKP_HIP(hipStreamWaitEvent(st, lane->ws[w].done, 0));
-    }
-  }
-
   // one witness map per proof on the main stream, each in its own abc region of the lane
   void witness_maps() {
     timer.tic();
-    with_fr(pk->curve, [&](auto P) {
-      for (int g = 0; g < G; g++) {
-        uint32_t* hg = witness_map_dev<decltype(P)>(ctx, pk, S + g * s_stride * 8, !pk->h_lagrange, g, G);
-        if (g == 0) h = hg;
-        ZKP_REQUIRE(hg == h + (size_t)g * h_stride * 8, ZKP_ERR_BAD_ARG);     // h sits at the same place in every region
-      }
-    });
+    for (int g = 0; g < G; g++) {
+      uint32_t* hg = witness_map_dev(ctx, pk, S + g * s_stride * 8, !pk->h_lagrange, g, G);
+      if (g == 0) h = hg;
+      ZKP_REQUIRE(hg == h + (size_t)g * h_stride * 8, ZKP_ERR_BAD_ARG);     // h sits at the same place in every region
+    }
     timer.toc(&timer.tm.ms_witness_map);
   }
 
@@ -410,7 +443,6 @@ struct ProofRun {
   // sort_src / l1_src: the workspace whose bucket sort / level-1 pass it reuses; defer / acc_into: the L -> H bucket chain (MsmJob)
   void msm(int idx, int ws, int sort_src = -1, int l1_src = -1, bool defer = false, int acc_into = -1) {
     static const char* const names[5] = {"A", "B1", "B2", "H", "L"};
-    const uint64_t handles[5] = {pk->hA, pk->hB1, pk->hB2, pk->hH, pk->hL};
     const bool on_h = idx == 3;                          // H runs over the witness map's output, the others over slices of S
     float ms = 0.f, ms_scan = 0.f;
     uint64_t entries = 0;
@@ -419,12 +451,7 @@ struct ProofRun {
 #ifdef ZKP_ABLATION   // timing ablation builds only (ZKP_BUILD_DEFS=-DZKP_ABLATION -> variants/<tag>/): WRONG proofs, never in the shipped library
     ctx->dbg_skip_k8 = ((tune.debug_skip_k8_mask >> idx) & 1) && ctx->batch_mode;
 #endif
-    MsmJob m;
-    m.handle = handles[idx];
-    m.scalars_dev = reinterpret_cast<const uint64_t*>(on_h ? h : S) + 4 * pk->q_lo[idx];
-    m.n = pk->q_n[idx];
-    m.montgomery = true;
-    m.out_dev_xyzz = res + idx * slot;
+    MsmJob m = proof_query_job(pk, idx, on_h ? h : S, res, slot);
     m.ms_accumulate = timer.on ? &ms : nullptr;
     m.ms_scan = timer.on ? &ms_scan : nullptr;
     m.n_entries = &entries;
@@ -829,561 +856,6 @@ void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint6
     throw;
   }
   select(0);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Single-process multi-GPU (BASELINE configs[4]): the caller of `create_proof` (prover.rs:124) is ONE
-// process, so the library owns one context per device (zkp_ctx_create_multi) and the exchange step itself.
-//   shard      every (extended) query is split by index over the devices (rank k keeps 1/n of the window tables); one proof
-//              uses all devices: partial MSMs per device -> partial sums gathered on device 0 over xGMI (peer copies of
-//              n x 1.25 KiB; optionally an RCCL all-gather) -> fold + assembly on device 0.  With >= 3 devices the witness map
-//              is task-split: the three independent chains of r1cs_to_qap.rs:144-162 (A z / B z / C z -> ifft -> coset_fft) run
-//              on devices 0 / 1 / 2, the b and c coset evaluations are gathered on device 0 (pointwise step + coset_ifft), and
-//              every device receives its slice of h for its share of the H MSM.
-//   replicate  full key on every device, independent proofs dealt round-robin, one host thread per device driving that
-//              device's pipelined lanes (zkp_groth16_prove_batch semantics).
-// Everything is enqueued from the calling thread with streams and cross-device events; device ids may repeat (several ranks
-// on ONE GPU: the tests on a one-GPU box), peer copies then degenerate to device-to-device copies.
-}  // namespace zkp
-#include <dlfcn.h>
-
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <string>
-
-#include <thread>
-struct zkp_groth16_pk_multi {
-  int mode = 0, curve = 0;
-  std::vector<zkp_groth16_pk*> pk;          // one per device of the root context, rank order
-  std::vector<hipEvent_t> ev_chain, ev_done, ev_h_read;
-  hipEvent_t ev_h = nullptr;
-  void* gathered = nullptr;                 // device 0: n x partials bytes
-  std::vector<void*> gathered_all;          // RCCL exchange: a receive buffer on every device
-  std::vector<void*> partial;               // per device: 5 XYZZ slots
-  // run-time choices of the sharded prover (zkp_groth16_multi_info): which exchange carried the last proof, and whether the
-  // three chains of the witness map are split over devices 0..2 — measured on this key's own first proofs, not assumed
-  int exchange = 0;                         // 0 = peer copies, 1 = RCCL all-gather, 2 = peer copies after the RCCL watchdog gave up
-  bool exchange_fallback = false;
-  int rccl_ranks = 0;
-  int split_choice = -1;                    // -1 undecided, 0 replicated witness map, 1 three-way split
-  int calls = 0;
-  double ms_variant[2] = {0.0, 0.0};        // wall time of a proof with the replicated / split witness map (calls 3 and 4)
-};
-namespace zkp {
-
-namespace {
-// RCCL all-gather of the partial sums, resolved at run time (no link-time dependency: the host may already have loaded its
-// own librccl).  Needs distinct devices.  Falls back to peer copies when unavailable.
-//
-// Watchdog (round 6).  The first multi-rank ncclCommInitAll and the first collective are the two places where a mis-configured
-// node HANGS instead of failing (no IPC handles, a dead link, a peer that never joins), and a hung create_proof is worse than a
-// slow one.  So the whole bring-up — dlopen, ncclCommInitAll, and a PROBE all-gather of 64 bytes per rank on throw-away streams
-// and buffers — runs on a helper thread; the calling thread waits for it with a deadline (zkp_ctx_config.multi_exchange_timeout_ms
-// / ZKP_MULTI_EXCHANGE_TIMEOUT_MS, default 30 s per stage).  The helper polls the probe's streams itself and, when they do not
-// drain in time, aborts the communicators (ncclCommAbort makes RCCL's kernels exit).  Either way — probe failed, or the helper
-// never came back — RCCL is marked unusable for the life of the process, the reason is printed once on stderr, the key's
-// zkp_groth16_multi_info says 2 ("peer copies after the RCCL watchdog"), and the partial sums travel by hipMemcpyPeerAsync.
-// The proof's streams only ever see an all-gather on communicators whose probe completed.
-// ZKP_DEBUG_RCCL_HANG=init | probe simulates the two hangs on any box (tests/test_gpu_multi.py).
-struct RcclApi {
-  struct Fns {
-    void* lib = nullptr;
-    int (*CommInitAll)(void**, int, const int*) = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    int (*CommAbort)(void*) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-  };
-  // what the helper thread and the caller share; the caller may walk away from it (shared_ptr keeps it alive for a helper
-  // that returns late)
-  struct Attempt {
-    std::mutex m;
-    std::condition_variable cv;
-    bool done = false, ok = false, abandoned = false;
-    Fns f;
-    std::vector<void*> comms;
-    std::string why;
-  };
-  Fns f;
-  std::mutex mu;                    // the communicators are process-wide: one bring-up, and one group of collective calls, at a time
-  // one set of communicators per device set, kept for the life of the process (a second root over other devices must not tear
-  // down the communicators a first root is about to use)
-  std::map<std::vector<int>, std::vector<void*>> comms_of;
-  bool unusable = false, watchdog_fired = false;
-  std::string why;
-
-  static void bring_up(std::shared_ptr<Attempt> at, std::vector<int> ids, int timeout_ms) {
-    const char* hang = env_str("ZKP_DEBUG_RCCL_HANG");     // read live: this helper thread has no context
-    Fns f;
-    std::vector<void*> comms(ids.size(), nullptr);
-    std::string why;
-    bool ok = false;
-    do {
-      for (const char* name : {"librccl.so", "librccl.so.1"})
-        if ((f.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL))) break;
-      if (!f.lib) { why = "librccl.so not loadable"; break; }
-      f.CommInitAll = reinterpret_cast<decltype(f.CommInitAll)>(dlsym(f.lib, "ncclCommInitAll"));
-      f.CommDestroy = reinterpret_cast<decltype(f.CommDestroy)>(dlsym(f.lib, "ncclCommDestroy"));
-      f.CommAbort = reinterpret_cast<decltype(f.CommAbort)>(dlsym(f.lib, "ncclCommAbort"));
-      f.GroupStart = reinterpret_cast<decltype(f.GroupStart)>(dlsym(f.lib, "ncclGroupStart"));
-      f.GroupEnd = reinterpret_cast<decltype(f.GroupEnd)>(dlsym(f.lib, "ncclGroupEnd"));
-      f.AllGather = reinterpret_cast<decltype(f.AllGather)>(dlsym(f.lib, "ncclAllGather"));
-      if (!f.CommInitAll || !f.CommDestroy || !f.GroupStart || !f.GroupEnd || !f.AllGather) { why = "librccl.so lacks a symbol"; break; }
-      if (hang && !strcmp(hang, "init")) std::this_thread::sleep_for(std::chrono::hours(24));      // simulated: ncclCommInitAll never returns
-      if (f.CommInitAll(comms.data(), (int)ids.size(), ids.data()) != 0) { why = "ncclCommInitAll failed"; comms.clear(); break; }
-      // probe: one all-gather of 64 bytes per rank on streams and buffers nothing else uses
-      const int n = (int)ids.size();
-      std::vector<hipStream_t> st(n, nullptr);
-      std::vector<void*> snd(n, nullptr), rcv(n, nullptr);
-      bool issued = true;
-      for (int k = 0; k < n && issued; k++)
-        issued = hipSetDevice(ids[k]) == hipSuccess && hipStreamCreateWithFlags(&st[k], hipStreamNonBlocking) == hipSuccess &&
-                 hipMalloc(&snd[k], 64) == hipSuccess && hipMalloc(&rcv[k], 64 * (size_t)n) == hipSuccess &&
-                 hipMemsetAsync(snd[k], k + 1, 64, st[k]) == hipSuccess;
-      if (issued) {
-        issued = f.GroupStart() == 0;
-        for (int k = 0; k < n && issued; k++)
-          issued = hipSetDevice(ids[k]) == hipSuccess && f.AllGather(snd[k], rcv[k], 64, /*ncclUint8*/ 1, comms[k], st[k]) == 0;
-        issued = f.GroupEnd() == 0 && issued;
-      }
-      bool drained = false, right = true;
-      if (issued) {
-        const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(timeout_ms);
-        while (!drained && std::chrono::steady_clock::now() < deadline) {
-          drained = !(hang && !strcmp(hang, "probe"));                                     // simulated: the collective never completes
-          for (int k = 0; k < n && drained; k++) drained = hipStreamQuery(st[k]) == hipSuccess;
-          if (!drained) std::this_thread::sleep_for(std::chrono::milliseconds(2));
-        }
-        if (drained) {                                                                   // every rank holds byte k + 1 in slot k
-          std::vector<uint8_t> got(64 * (size_t)n);
-          for (int k = 0; k < n && right; k++) {
-            right = hipSetDevice(ids[k]) == hipSuccess && hipMemcpy(got.data(), rcv[k], got.size(), hipMemcpyDeviceToHost) == hipSuccess;
-            for (int j = 0; j < n && right; j++) right = got[64 * (size_t)j] == (uint8_t)(j + 1) && got[64 * (size_t)j + 63] == (uint8_t)(j + 1);
-          }
-        }
-      }
-      if (!issued || !drained || !right) {
-        why = !issued ? "the probe all-gather could not be enqueued" : !drained ? "the probe all-gather did not complete within " + std::to_string(timeout_ms) + " ms"
-                      : "the probe all-gather returned wrong bytes";
-        for (void* c : comms)
-          if (c) (void)(f.CommAbort ? f.CommAbort(c) : f.CommDestroy(c));
-        comms.clear();
-        if (!drained) break;                                                             // streams may still be wedged: leak the probe's resources
-      }
-      for (int k = 0; k < n; k++) {
-        (void)hipSetDevice(ids[k]);
-        if (st[k]) (void)hipStreamDestroy(st[k]);
-        if (snd[k]) (void)hipFree(snd[k]);
-        if (rcv[k]) (void)hipFree(rcv[k]);
-      }
-      ok = issued && drained && right;
-    } while (false);
-    std::lock_guard<std::mutex> lk(at->m);
-    if (at->abandoned) {                                  // the caller gave up on this attempt: nobody will use these communicators
-      for (void* c : comms)
-        if (c && f.CommAbort) (void)f.CommAbort(c);
-      return;
-    }
-    at->f = f;
-    at->comms = ok ? comms : std::vector<void*>();
-    at->ok = ok;
-    at->why = why;
-    at->done = true;
-    at->cv.notify_all();
-  }
-
-  // -> the communicators of this device set (rank order), or nullptr
-  const std::vector<void*>* ready(const std::vector<zkp_ctx*>& devs, int timeout_ms) {
-    if (unusable) return nullptr;
-    std::vector<int> ids;
-    for (zkp_ctx* d : devs) ids.push_back(d->device);
-    if (auto it = comms_of.find(ids); it != comms_of.end()) return &it->second;
-    for (size_t i = 0; i < ids.size(); i++)
-      for (size_t j = i + 1; j < ids.size(); j++)
-        if (ids[i] == ids[j]) { why = "duplicate device ids"; return nullptr; }           // RCCL refuses duplicate devices (not sticky)
-    timeout_ms = std::max(1, timeout_ms);
-    auto at = std::make_shared<Attempt>();
-    std::thread(bring_up, at, ids, timeout_ms).detach();
-    std::unique_lock<std::mutex> lk(at->m);
-    // two stages on the helper (communicator setup, probe), one deadline each, and a margin for the teardown
-    const bool back = at->cv.wait_for(lk, std::chrono::milliseconds(2 * (long long)timeout_ms + 2000), [&] { return at->done; });
-    if (!back) {
-      at->abandoned = true;
-      unusable = watchdog_fired = true;
-      why = "RCCL bring-up (ncclCommInitAll + probe all-gather) did not return within " + std::to_string(2 * (long long)timeout_ms + 2000) + " ms";
-      return nullptr;
-    }
-    f = at->f;
-    if (!at->ok) {
-      why = at->why;
-      // a missing library is an ordinary "unavailable"; a failed init or probe is what the watchdog exists for
-      unusable = true;
-      watchdog_fired = f.lib != nullptr && at->why != "librccl.so lacks a symbol";
-      return nullptr;
-    }
-    return &(comms_of[ids] = at->comms);
-  }
-};
-RcclApi& rccl() {
-  static RcclApi* api = new RcclApi();      // never destructed: communicators must not be torn down after the HIP runtime
-  return *api;
-}
-
-void copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t st) {
-  if (!bytes) return;
-  if (dst_dev == src_dev) ZKP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
-  else ZKP_HIP(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, st));
-}
-
-// one of the three chains of the witness map (k = 0 / 1 / 2: a / b / c), on ctx's current stream; result in region k of abc
-template <class P>
-void witness_chain(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, int k) {
-  const uint32_t N = (uint32_t)pk->N;
-  uint32_t* abc = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8);
-  uint32_t* buf = abc + (size_t)k * pk->N * 8;
-  hipLaunchKernelGGL(csr_eval_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, ctx->cur->stream, pk->m[k].row_ptr, pk->m[k].col,
-                     pk->m[k].coeff, z_dev, pk->num_constraints, N, pk->num_inputs, k == 0 ? 1 : 0, buf);
-  if (!ntt_ifft_coset_fft(ctx, pk->curve, buf, pk->log_n)) {
-    ntt_run(ctx, pk->curve, buf, pk->log_n, ZKP_NTT_IFFT);
-    ntt_run(ctx, pk->curve, buf, pk->log_n, ZKP_NTT_COSET_FFT);
-  }
-  ZKP_HIP(hipGetLastError());
-}
-// second half of the witness map (pointwise step + coset_ifft) over the three regions of abc; returns h
-template <class P>
-uint32_t* witness_tail(zkp_ctx* ctx, zkp_groth16_pk* pk) {
-  const uint32_t N = (uint32_t)pk->N;
-  uint32_t* a = pk->lane[ctx->cur_idx].abc.as<uint32_t>(3 * pk->N * 8);
-  uint32_t* b = a + pk->N * 8;
-  uint32_t* c = b + pk->N * 8;
-  if (pk->h_lagrange) {                                      // evaluation-form key: the H MSM takes the pointwise values
-    if (pk->c_folded)
-      hipLaunchKernelGGL(qap_pointwise_ab_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, ctx->cur->stream, a, b,
-                         pk->consts.as<uint32_t>(64), N);
-    else
-    hipLaunchKernelGGL(qap_pointwise_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, ctx->cur->stream, a, b, c,
-                       pk->consts.as<uint32_t>(64), N);
-    ZKP_HIP(hipGetLastError());
-    return a;
-  }
-  if (uint32_t* hq = ntt_qap_coset_ifft(ctx, pk->curve, a, b, c, pk->consts.as<uint32_t>(64), pk->log_n)) return hq;
-  hipLaunchKernelGGL(qap_pointwise_kernel<P>, dim3((N + 255) / 256), dim3(256), 0, ctx->cur->stream, a, b, c,
-                     pk->consts.as<uint32_t>(64), N);
-  ntt_run(ctx, pk->curve, a, pk->log_n, ZKP_NTT_COSET_IFFT);
-  ZKP_HIP(hipGetLastError());
-  return a;
-}
-
-template <class FrP>
-void prove_multi_t(zkp_ctx* root, zkp_groth16_pk_multi* M, const uint64_t* const* z, bool z_on_device, const uint64_t* r,
-                   const uint64_t* s, uint64_t* proof_out, uint8_t* inf_out) {
-  const int n = (int)root->devs.size();
-  const MsmVtbl* v2 = msm_vtbl(M->curve, 2);
-  const size_t slot = v2->xyzz_bytes, pb = 5 * slot;
-  // Witness map: replicated on every device, or its a / b / c chains on devices 0 / 1 / 2 with two N x 32-byte vectors shipped to
-  // device 0 and the slices of h shipped back (n >= 3).  Which one is faster depends on the link (one xGMI hop vs. a PCIe switch)
-  // and on the domain, so the key MEASURES it: proofs 1-2 warm both variants up, proofs 3-4 time them (wall clock of the whole
-  // call, same witness), from proof 5 on the faster one runs.  The proof bytes do not depend on the choice.
-  // ZKP_MULTI_WM_SPLIT=0 / 1 forces a variant.
-  const int split_env = root->cfg.multi_wm_split;               // zkp_ctx_config.multi_witness_split / ZKP_MULTI_WM_SPLIT
-  bool split = false;
-  const int call = M->calls++;
-  if (n >= 3) {
-    if (split_env >= 0) M->split_choice = split_env ? 1 : 0;
-    if (M->split_choice >= 0) split = M->split_choice == 1;
-    else split = (call & 1) == 1;                                   // calls 0, 2: replicated; 1, 3: split
-  } else {
-    M->split_choice = 0;
-  }
-  const auto t_call = std::chrono::steady_clock::now();
-  // Exchange: RCCL all-gather (the exchange BASELINE.json names) whenever the devices are distinct and librccl loads; peer copies
-  // otherwise, said once on stderr.  ZKP_MULTI_EXCHANGE=peer / rccl forces one.
-  // ZKP_MULTI_EXCHANGE=rccl also takes the RCCL branch with ONE rank (a one-rank ncclCommInitAll + ncclAllGather is legal): the
-  // hand-declared prototypes below get executed on a one-GPU box (tests/test_gpu_multi.py) before any 8-GPU node sees them.
-  const int want = root->cfg.multi_exchange;                     // zkp_ctx_config.multi_exchange / ZKP_MULTI_EXCHANGE, per context
-  bool use_rccl = false;
-  const std::vector<void*>* rccl_comms = nullptr;
-  if ((n > 1 && want != ZKP_EXCHANGE_PEER) || (n == 1 && want == ZKP_EXCHANGE_RCCL)) {
-    std::lock_guard<std::mutex> lk(rccl().mu);
-    rccl_comms = rccl().ready(root->devs, root->cfg.multi_exchange_timeout_ms);
-    use_rccl = rccl_comms != nullptr;
-    static bool told = false;
-    if (!use_rccl && !told) {
-      told = true;
-      fprintf(stderr, "[zkp_accel] sharded prover: RCCL all-gather unavailable (%s)%s — the partial sums travel by peer copies\n",
-              rccl().why.c_str(), rccl().watchdog_fired ? " [watchdog: RCCL stays off for this process]" : "");
-    }
-    if (!use_rccl && rccl().watchdog_fired) M->exchange_fallback = true;
-  }
-  M->exchange = use_rccl ? 1 : (M->exchange_fallback ? 2 : 0);
-  M->rccl_ranks = use_rccl ? n : 0;
-  std::vector<uint32_t*> S(n), h(n, nullptr);
-  std::vector<char*> res(n);
-  // phase 1 — every device: inputs, the four z-MSMs over its slices on the MSM streams, its part of the witness map
-  for (int k = 0; k < n; k++) {
-    zkp_ctx* ctx = root->devs[k];
-    zkp_groth16_pk* pk = M->pk[k];
-    ZKP_HIP(hipSetDevice(ctx->device));
-    ctx->cur = &ctx->lanes[0];
-    ctx->cur_idx = 0;
-    hipStream_t st = ctx->cur->stream;
-    zkp_groth16_pk::PerLane& PL = pk->lane[0];
-    S[k] = PL.S.as<uint32_t>((pk->nz + 4) * 8);
-    uint32_t* rs = PL.proof.as<uint32_t>(1024);
-    res[k] = reinterpret_cast<char*>(PL.results.get(6 * slot));
-    const uint64_t* zk = z_on_device ? z[k] : z[0];
-    ZKP_HIP(hipMemcpyAsync(S[k], zk, pk->nz * 32, z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    ZKP_HIP(hipMemcpyAsync(rs, r, 32, hipMemcpyHostToDevice, st));
-    ZKP_HIP(hipMemcpyAsync(rs + 8, s, 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(scalar_tail_kernel<FrP>, dim3(1), dim3(64), 0, st, S[k] + pk->nz * 8, rs, (size_t)0);
-    ZKP_HIP(hipEventRecord(ctx->cur->ev_fork, st));
-    for (int w = 1; w < zkp_ctx::N_WS; w++) ZKP_HIP(hipStreamWaitEvent(ctx->cur->ws[w].stream, ctx->cur->ev_fork, 0));
-    if (!split) h[k] = witness_map_dev<FrP>(ctx, pk, S[k], !pk->h_lagrange);
-    else if (k < (pk->c_folded ? 2 : 3)) {                           // C folded into the L query: no c chain
-      witness_chain<FrP>(ctx, pk, S[k], k);
-      ZKP_HIP(hipEventRecord(M->ev_chain[k], st));
-    }
-    const uint64_t* Sd = reinterpret_cast<const uint64_t*>(S[k]);
-    auto run = [&](int idx, uint64_t handle, int w, int sort_src, int l1_src) {
-      MsmJob job;
-      job.handle = handle;
-      job.scalars_dev = Sd + 4 * pk->q_lo[idx];
-      job.n = pk->q_n[idx];
-      job.montgomery = true;
-      job.out_dev_xyzz = res[k] + idx * slot;
-      job.ws = w;
-      job.sort_src = sort_src;
-      job.l1_src = l1_src;
-      msm_run(ctx, job);
-    };
-    const int l1 = pk->share_l1 ? 1 : -1;
-    const bool b_l1 = pk->share_l1 && pk->b_in_l1;
-    if (!b_l1) run(2, pk->hB2, 2, -1, -1);
-    run(0, pk->hA, 1, -1, -1);
-    if (b_l1) run(2, pk->hB2, 2, -1, l1);
-    run(1, pk->hB1, 3, pk->share_b_sort ? 2 : -1, -1);
-    run(4, pk->hL, 1, pk->share_al_sort ? 1 : -1, l1);
-  }
-  // phase 2 (task-split witness map) — device 0 gathers b and c, finishes h, every device fetches its slice of h
-  if (split) {
-    zkp_ctx* c0 = root->devs[0];
-    zkp_groth16_pk* p0 = M->pk[0];
-    ZKP_HIP(hipSetDevice(c0->device));
-    hipStream_t st0 = c0->cur->stream;
-    uint32_t* abc0 = p0->lane[0].abc.as<uint32_t>(3 * p0->N * 8);
-    const int nch = p0->c_folded ? 2 : 3;
-    for (int k = 1; k < nch; k++) {
-      zkp_groth16_pk* pk = M->pk[k];
-      const uint32_t* src = pk->lane[0].abc.as<uint32_t>(3 * pk->N * 8) + (size_t)k * pk->N * 8;
-      ZKP_HIP(hipStreamWaitEvent(st0, M->ev_chain[k], 0));
-      copy_between(abc0 + (size_t)k * p0->N * 8, c0->device, src, root->devs[k]->device, p0->N * 32, st0);
-    }
-    h[0] = witness_tail<FrP>(c0, p0);
-    ZKP_HIP(hipEventRecord(M->ev_h, st0));
-    for (int k = 1; k < n; k++) {
-      zkp_ctx* ctx = root->devs[k];
-      zkp_groth16_pk* pk = M->pk[k];
-      ZKP_HIP(hipSetDevice(ctx->device));
-      hipStream_t st = ctx->cur->stream;
-      h[k] = pk->lane[0].abc.as<uint32_t>(3 * pk->N * 8);        // region a of this device (its own chain, if any, is consumed)
-      ZKP_HIP(hipStreamWaitEvent(st, M->ev_h, 0));
-      if (k < nch) ZKP_HIP(hipStreamWaitEvent(st, M->ev_chain[k], 0));
-      copy_between(h[k] + pk->q_lo[3] * 8, ctx->device, h[0] + pk->q_lo[3] * 8, c0->device, pk->q_n[3] * 32, st);
-      ZKP_HIP(hipEventRecord(M->ev_h_read[k], st));
-    }
-  }
-  // phase 3 — every device: H MSM over its slice of h, join, partial sums
-  for (int k = 0; k < n; k++) {
-    zkp_ctx* ctx = root->devs[k];
-    zkp_groth16_pk* pk = M->pk[k];
-    ZKP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->cur->stream;
-    MsmJob job;
-    job.handle = pk->hH;
-    job.scalars_dev = reinterpret_cast<const uint64_t*>(h[k]) + 4 * pk->q_lo[3];
-    job.n = pk->q_n[3];
-    job.montgomery = true;
-    job.out_dev_xyzz = res[k] + 3 * slot;
-    msm_run(ctx, job);
-    for (int w = 1; w < zkp_ctx::N_WS; w++) {
-      ZKP_HIP(hipEventRecord(ctx->cur->ws[w].done, ctx->cur->ws[w].stream));
-      ZKP_HIP(hipStreamWaitEvent(st, ctx->cur->ws[w].done, 0));
-    }
-    ZKP_HIP(hipMemcpyAsync(M->partial[k], res[k], pb, hipMemcpyDeviceToDevice, st));
-    ZKP_HIP(hipEventRecord(M->ev_done[k], st));
-  }
-  // phase 4 — exchange (n x 1.25 KiB for BN254: latency-bound on any topology) + fold + assembly on device 0
-  zkp_ctx* c0 = root->devs[0];
-  const void* gathered = M->gathered;
-  if (use_rccl) {
-    RcclApi& R = rccl();
-    // two roots over the same devices share these communicators (two prover threads of one process): their groups are enqueued one
-    // after the other, in the same order on every rank
-    std::lock_guard<std::mutex> lk(R.mu);
-    ZKP_REQUIRE(R.f.GroupStart() == 0, ZKP_ERR_DEVICE);
-    for (int k = 0; k < n; k++) {
-      ZKP_HIP(hipSetDevice(root->devs[k]->device));
-      ZKP_REQUIRE(R.f.AllGather(M->partial[k], M->gathered_all[k], pb, /*ncclUint8*/ 1, (*rccl_comms)[k], root->devs[k]->cur->stream) == 0,
-                  ZKP_ERR_DEVICE);
-    }
-    ZKP_REQUIRE(R.f.GroupEnd() == 0, ZKP_ERR_DEVICE);
-    gathered = M->gathered_all[0];
-    ZKP_HIP(hipSetDevice(c0->device));
-  } else {
-    ZKP_HIP(hipSetDevice(c0->device));
-    hipStream_t st0 = c0->cur->stream;
-    for (int k = 0; k < n; k++) {
-      if (k) ZKP_HIP(hipStreamWaitEvent(st0, M->ev_done[k], 0));
-      copy_between((char*)M->gathered + (size_t)k * pb, c0->device, M->partial[k], root->devs[k]->device, pb, st0);
-    }
-  }
-  if (split)                                     // h on device 0 must outlive the slice reads of the other devices
-    for (int k = 1; k < n; k++) ZKP_HIP(hipStreamWaitEvent(c0->cur->stream, M->ev_h_read[k], 0));
-  groth16_fold_assemble(c0, M->curve, gathered, n, r, s, proof_out, inf_out);        // synchronises device 0's stream
-  for (int k = 1; k < n; k++) {                  // the next call reuses every device's buffers
-    ZKP_HIP(hipSetDevice(root->devs[k]->device));
-    ZKP_HIP(hipStreamSynchronize(root->devs[k]->cur->stream));
-  }
-  ZKP_HIP(hipSetDevice(c0->device));
-  if (n >= 3 && M->split_choice < 0 && call >= 2) {
-    M->ms_variant[split ? 1 : 0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    if (call >= 3) M->split_choice = M->ms_variant[1] < M->ms_variant[0] ? 1 : 0;
-  }
-}
-}  // namespace
-
-zkp_groth16_pk_multi* groth16_pk_upload_multi(zkp_ctx* root, const zkp_groth16_pk_desc* d, int mode) {
-  ZKP_REQUIRE(!root->devs.empty() && (mode == 0 || mode == 1), ZKP_ERR_BAD_ARG);
-  const int n = (int)root->devs.size();
-  std::unique_ptr<zkp_groth16_pk_multi> M(new zkp_groth16_pk_multi());
-  M->mode = mode;
-  M->curve = d->curve;
-  KeepLagrange keep_lagrange;                      // one transform of the H query serves every device (groth16_pk.hpp)
-  try {
-    for (int k = 0; k < n; k++) {
-      zkp_ctx* ctx = root->devs[k];
-      ZKP_HIP(hipSetDevice(ctx->device));
-      M->pk.push_back(mode == 0 ? groth16_pk_upload(ctx, d, k, n) : groth16_pk_upload(ctx, d, 0, 0));
-      hipEvent_t e;
-      ZKP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      M->ev_chain.push_back(e);
-      ZKP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      M->ev_done.push_back(e);
-      ZKP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      M->ev_h_read.push_back(e);
-      void* p = nullptr;
-      if (hipMalloc(&p, groth16_partials_bytes(d->curve)) != hipSuccess) throw StatusError{ZKP_ERR_OOM};
-      M->partial.push_back(p);
-      p = nullptr;
-      if (hipMalloc(&p, (size_t)n * groth16_partials_bytes(d->curve)) != hipSuccess) throw StatusError{ZKP_ERR_OOM};
-      M->gathered_all.push_back(p);
-    }
-    ZKP_HIP(hipSetDevice(root->device));
-    ZKP_HIP(hipEventCreateWithFlags(&M->ev_h, hipEventDisableTiming));
-    M->gathered = M->gathered_all[0];
-  } catch (...) {
-    groth16_pk_multi_free(root, M.release());
-    throw;
-  }
-  return M.release();
-}
-
-void groth16_pk_multi_free(zkp_ctx* root, zkp_groth16_pk_multi* M) {
-  for (size_t k = 0; k < M->pk.size(); k++) {
-    (void)hipSetDevice(root->devs[k]->device);
-    if (M->pk[k]) groth16_pk_free(root->devs[k], M->pk[k]);
-  }
-  for (size_t k = 0; k < M->partial.size(); k++) {
-    (void)hipSetDevice(root->devs[k]->device);
-    if (M->partial[k]) (void)hipFree(M->partial[k]);
-  }
-  for (size_t k = 0; k < M->gathered_all.size(); k++) {
-    (void)hipSetDevice(root->devs[k]->device);
-    if (M->gathered_all[k]) (void)hipFree(M->gathered_all[k]);
-  }
-  for (auto& v : {M->ev_chain, M->ev_done, M->ev_h_read})
-    for (hipEvent_t e : v)
-      if (e) (void)hipEventDestroy(e);
-  if (M->ev_h) (void)hipEventDestroy(M->ev_h);
-  (void)hipSetDevice(root->device);
-  delete M;
-}
-
-// info[0] = exchange of the last proof (0 peer copies, 1 RCCL all-gather), [1] = RCCL ranks, [2] = witness map (0 replicated, 1 split
-// over devices 0..2, 2 = still measuring), [3] / [4] = microseconds of the timed proof with the replicated / split map, [5] = devices
-void groth16_multi_info(zkp_ctx* root, zkp_groth16_pk_multi* M, uint64_t info[6]) {
-  info[0] = (uint64_t)M->exchange;
-  info[1] = (uint64_t)M->rccl_ranks;
-  info[2] = M->split_choice < 0 ? 2 : (uint64_t)M->split_choice;
-  info[3] = (uint64_t)(M->ms_variant[0] * 1e3);
-  info[4] = (uint64_t)(M->ms_variant[1] * 1e3);
-  info[5] = (uint64_t)root->devs.size();
-}
-
-void groth16_prove_multi(zkp_ctx* root, zkp_groth16_pk_multi* M, const uint64_t* const* z, bool z_on_device,
-                         const uint64_t* r, const uint64_t* s, uint64_t* proof_out, uint8_t* inf_out) {
-  ZKP_REQUIRE(M->mode == 0 && M->pk.size() == root->devs.size() && !root->devs.empty(), ZKP_ERR_BAD_ARG);
-  try {
-    with_fr(M->curve, [&](auto P) { prove_multi_t<decltype(P)>(root, M, z, z_on_device, r, s, proof_out, inf_out); });
-  } catch (...) {
-    for (zkp_ctx* c : root->devs) {
-      (void)hipSetDevice(c->device);
-      (void)hipDeviceSynchronize();
-    }
-    (void)hipSetDevice(root->device);
-    throw;
-  }
-}
-
-// Throughput mode on every device of the root context: proof i runs on device i % n (its witness pointer, when
-// z_on_device, lives there); one host thread per device drives that device's lanes exactly as zkp_groth16_prove_batch does.
-void groth16_prove_batch_multi(zkp_ctx* root, zkp_groth16_pk_multi* M, size_t count, const uint64_t* const* z,
-                               bool z_on_device, const uint64_t* r, const uint64_t* s, uint64_t* proofs_out,
-                               uint8_t* inf_out) {
-  ZKP_REQUIRE(M->mode == 1 && M->pk.size() == root->devs.size() && !root->devs.empty(), ZKP_ERR_BAD_ARG);
-  const int n = (int)root->devs.size();
-  const MsmVtbl* v1 = msm_vtbl(M->curve, 1);
-  const MsmVtbl* v2 = msm_vtbl(M->curve, 2);
-  const size_t pw64 = (4 * (size_t)v1->fN + 2 * (size_t)v2->fN) / 2;
-  std::vector<int32_t> status(n, ZKP_OK);
-  std::vector<std::thread> th;
-  for (int k = 0; k < n; k++) {
-    th.emplace_back([&, k] {
-      try {
-        zkp_ctx* ctx = root->devs[k];
-        ZKP_HIP(hipSetDevice(ctx->device));
-        std::vector<const uint64_t*> zk;
-        std::vector<uint64_t> rk, sk;
-        for (size_t i = (size_t)k; i < count; i += (size_t)n) {
-          zk.push_back(z[i]);
-          rk.insert(rk.end(), r + 4 * i, r + 4 * i + 4);
-          sk.insert(sk.end(), s + 4 * i, s + 4 * i + 4);
-        }
-        if (zk.empty()) return;
-        std::vector<uint64_t> po(zk.size() * pw64);
-        std::vector<uint8_t> io(zk.size() * 3);
-        groth16_prove_batch(ctx, M->pk[k], zk.size(), zk.data(), rk.data(), sk.data(), po.data(), io.data(), z_on_device);
-        size_t j = 0;
-        for (size_t i = (size_t)k; i < count; i += (size_t)n, j++) {
-          memcpy(proofs_out + i * pw64, po.data() + j * pw64, pw64 * 8);
-          memcpy(inf_out + i * 3, io.data() + j * 3, 3);
-        }
-      } catch (const StatusError& e) {
-        status[k] = e.status;
-      } catch (const HipError& e) {
-        fprintf(stderr, "[zkp_accel] HIP error %s at line %d: %s (device rank %d)\n", hipGetErrorString(e.e), e.line, e.what, k);
-        status[k] = e.e == hipErrorOutOfMemory ? ZKP_ERR_OOM : ZKP_ERR_DEVICE;
-      } catch (...) {
-        status[k] = ZKP_ERR_DEVICE;
-      }
-    });
-  }
-  for (auto& t : th) t.join();
-  (void)hipSetDevice(root->device);
-  for (int32_t st : status)
-    if (st != ZKP_OK) throw StatusError{st};
 }
 
 }  // namespace zkp

@@ -1,7 +1,7 @@
 // The Groth16 proving key on the device: everything that builds, describes or frees a zkp_groth16_pk (groth16_pk.hpp).  The upload
 // is a KeyBuild, phase by phase: the circuit's matrices, the slices and window plan of the whole key, the five query tables (the H
 // query in evaluation form and C folded into the L query unless the key is kept as given), then which sorts and passes the prover's
-// MSMs share.  The provers that read the key are in groth16.hip.
+// MSMs share.  The provers that read the key are in groth16.hip and groth16_multi.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>

@@ -1,5 +1,6 @@
-// The device-resident Groth16 proving key: what groth16_key.hip builds, describes and frees and what the provers of groth16.hip read.
-// Private to those two units.
+// The device-resident Groth16 proving key: what groth16_key.hip builds, describes and frees and what the provers read — the
+// single-device prover of groth16.hip and the multi-device prover of groth16_multi.hip — and the steps of a proof that groth16.hip
+// (which holds the kernels) lends the multi-device prover.  Private to those three units.
 #pragma once
 #include <vector>
 
@@ -58,5 +59,20 @@ struct KeepLagrange {
   KeepLagrange(const KeepLagrange&) = delete;
   KeepLagrange& operator=(const KeepLagrange&) = delete;
 };
+
+// groth16.hip: the steps of one proof on a lane (comments at the definitions).  The witness map on ctx's current stream, as chain
+// k -> region k of an abc region and (a, b, c) -> h:
+void witness_eval(zkp_ctx* ctx, const zkp_groth16_pk* pk, const uint32_t* z_dev, int k, uint32_t* out);
+void witness_transform(zkp_ctx* ctx, const zkp_groth16_pk* pk, uint32_t* buf);
+uint32_t* witness_finish(zkp_ctx* ctx, zkp_groth16_pk* pk, uint32_t* a, bool coeffs);
+// the three composed: the whole map of proof g of a group of G in the g-th abc region of the current lane
+uint32_t* witness_map_dev(zkp_ctx* ctx, zkp_groth16_pk* pk, const uint32_t* z_dev, bool coeffs = true, int g = 0, int G = 1);
+// the inputs of a proof, the request of one of its five MSMs, the fork and the join of its lane's streams
+void proof_copy_inputs(hipStream_t st, const zkp_groth16_pk* pk, const uint64_t* z, bool z_on_device, const uint64_t* r,
+                       const uint64_t* s, uint32_t* S, uint32_t* rs);
+void proof_scalar_tails(hipStream_t st, const zkp_groth16_pk* pk, uint32_t* S, const uint32_t* rs, int G);
+MsmJob proof_query_job(const zkp_groth16_pk* pk, int idx, const uint32_t* scalars, char* res, size_t slot);
+void lane_fork(zkp_lane* lane);
+void lane_join(zkp_lane* lane);
 
 }  // namespace zkp

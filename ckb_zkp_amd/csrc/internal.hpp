@@ -1,8 +1,27 @@
 // Internal (non-ABI) entry points shared between translation units.
 #pragma once
+#include <new>
+
 #include "ctx.hpp"
 
 namespace zkp {
+
+// Inside a catch block: the status the C boundary reports for the exception in flight.  *hip receives a HipError (its `what` is then
+// non-null) so that the caller can print the line of its site.
+inline int32_t status_of_current_exception(HipError* hip = nullptr) {
+  try {
+    throw;
+  } catch (const StatusError& e) {
+    return e.status;
+  } catch (const HipError& e) {
+    if (hip) *hip = e;
+    return e.e == hipErrorOutOfMemory ? ZKP_ERR_OOM : ZKP_ERR_DEVICE;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  } catch (...) {
+    return ZKP_ERR_DEVICE;
+  }
+}
 
 // ntt.hip
 void ntt_run(zkp_ctx* ctx, int curve, uint32_t* data_dev, int log_n, int op);
@@ -144,7 +163,7 @@ void groth16_prove_batch(zkp_ctx* ctx, zkp_groth16_pk* pk, size_t n, const uint6
 void groth16_assemble(zkp_ctx* ctx, int curve, const uint64_t* sums_xyz, const uint64_t* r, const uint64_t* s,
                       uint64_t* proof_out, uint8_t* inf_out);
 
-// single-process multi-GPU (groth16.hip): `root` is a context made by zkp_ctx_create_multi; mode 0 = base-sharded key (one
+// single-process multi-GPU (groth16_multi.hip): `root` is a context made by zkp_ctx_create_multi; mode 0 = base-sharded key (one
 // proof over all devices), 1 = replicated key (independent proofs round-robin)
 zkp_groth16_pk_multi* groth16_pk_upload_multi(zkp_ctx* root, const zkp_groth16_pk_desc* d, int mode);
 void groth16_pk_multi_free(zkp_ctx* root, zkp_groth16_pk_multi* pk);

@@ -57,6 +57,63 @@ def test_prove_multi_sharded_equals_single_gpu(ctx, curve, k, world):
         pk.free()
 
 
+RS_PAIRS = ((0xABCDEF0123456789ABCDEF, 0x13579BDF02468ACE), (0, 0))
+
+
+@pytest.fixture(scope="module")
+def split_reference(ctx):
+    """The 2^10 BN254 instance of the key-form cases below and its single-GPU proofs (default key form), computed once."""
+    c = get_curve("bn254")
+    inst = mimc_chain_instance("bn254", samples_for_domain(10))
+    params = groth16.generate_parameters(ctx, "bn254", inst, **TOXIC)
+    z = codec.fr_to_mont(inst.z, c).reshape(-1, 4)
+    pk = groth16.ProvingKey(ctx, params, inst)
+    try:
+        proofs = []
+        for r_, s_ in RS_PAIRS:
+            rm, sm = codec.fr_to_mont([r_], c)[0], codec.fr_to_mont([s_], c)[0]
+            proofs.append((rm, sm) + tuple(pk.prove_raw(z, rm, sm)))
+    finally:
+        pk.free()
+    return inst, params, z, proofs
+
+
+@pytest.mark.parametrize("world", [3, 4])
+@pytest.mark.parametrize("form", [dict(h_evaluation_form=True, c_fold=False), dict(h_evaluation_form=False)],
+                         ids=["evaluation_unfolded", "coefficient"])
+def test_prove_multi_split_witness_map_key_forms(split_reference, form, world):
+    """The task-split witness map over the two key forms no default-config test selects: evaluation-form H with C not folded (three
+    chains, the three-operand pointwise step) and the coefficient-form key (three chains, the fused pointwise step + coset_ifft, h may
+    land in region b of device 0).  World 4 adds a rank that runs no chain and only fetches its slice of h.  The proof is byte-equal
+    to the single-GPU proof of the default key form."""
+    inst, params, z, proofs = split_reference
+    m = MultiContext([0] * world, dict(form, multi_witness_split=True))
+    try:
+        # the key form really selected: a whole key made on the same context carries the same configuration
+        whole = groth16.ProvingKey(m, params, inst)
+        try:
+            plan = whole.table_plan()
+            assert plan["h_evaluation_form"] == form["h_evaluation_form"] and plan["c_folded_into_l"] is False
+        finally:
+            whole.free()
+        mpk = groth16.MultiProvingKey(m, params, inst, groth16.MULTI_SHARD)
+        try:
+            zds = [m.member(r).to_device(z) for r in range(world)]
+            for (r_, s_), (rm, sm, out1, inf1) in zip(RS_PAIRS, proofs):
+                for rep in range(2):                                # the second call reuses every buffer
+                    out2, inf2 = mpk.prove_raw(z, rm, sm)
+                    assert np.array_equal(out1, out2) and np.array_equal(inf1, inf2), (r_, s_, rep)
+                out3, inf3 = mpk.prove_raw(zds, rm, sm, z_on_device=True)
+                assert np.array_equal(out1, out3) and np.array_equal(inf1, inf3), (r_, s_)
+            for r, d in enumerate(zds):
+                m.member(r).dev_free(d)
+            assert mpk.info()["witness_map"] == "split over devices 0..2"
+        finally:
+            mpk.free()
+    finally:
+        m.close()
+
+
 def test_prove_multi_replicated_witness_map(ctx, monkeypatch):
     """ZKP_MULTI_WM_SPLIT=0 is read when a context is created (zkp_cfg): the replicated-witness-map variant of the 3-rank step runs
     in a child process of its own and must print the same proof as the task-split one."""
@@ -86,7 +143,7 @@ print("PROOF", out.tobytes().hex(), inf.tobytes().hex())
 
 def test_prove_multi_one_rank_through_rccl(ctx):
     """VERDICT r4 task 5: the RCCL branch of zkp_groth16_prove_multi (dlsym'd ncclCommInitAll / ncclGroupStart / ncclAllGather /
-    ncclGroupEnd, csrc/groth16.hip) EXECUTED on the one GPU this box has: ZKP_MULTI_EXCHANGE=rccl with a one-rank multi context
+    ncclGroupEnd, csrc/rccl_gather.hip) EXECUTED on the one GPU this box has: ZKP_MULTI_EXCHANGE=rccl with a one-rank multi context
     (a one-rank communicator is legal), the proof equals the plain single-GPU proof and zkp_groth16_multi_info reports
     exchange = rccl, rccl_ranks = 1.  A child process, so that a misbehaving communicator cannot wedge the suite."""
     code = r'''
