@@ -202,6 +202,11 @@ SIGNATURES = {
     "zkp_fr_mimc_trace_dev": (C.c_int32, [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]),
     "zkp_fr_merkle_tree_dev": (C.c_int32, [vp, vp, C.c_int32, vp, C.c_size_t]),
     "zkp_fr_merkle_paths_dev": (C.c_int32, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "zkp_sha256_info": (C.c_int32, [u64p]),
+    "zkp_sha256_dev": (C.c_int32, [vp, vp, C.c_size_t, C.c_size_t, vp]),
+    "zkp_sha256_trace_dev": (C.c_int32, [vp, vp, C.c_size_t, C.c_size_t, vp]),
+    "zkp_sha256_merkle_tree_dev": (C.c_int32, [vp, vp, C.c_size_t]),
+    "zkp_fr_bits_expand_dev": (C.c_int32, [vp, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t]),
     "zkp_fr_prefix_product_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_size_t, vp]),
     "zkp_fr_plonk_perm_z_dev": (C.c_int32, [vp, C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
     "zkp_fr_plonk_quotient_dev": (C.c_int32, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),

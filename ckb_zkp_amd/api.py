@@ -621,6 +621,26 @@ class Context:
         _lib.check(self.lib.zkp_fr_merkle_paths_dev(self.h, C.c_void_p(nodes_ptr or 0), n, C.c_void_p(leaf_idx_ptr or 0), q,
                                                     C.c_void_p(out_ptr or 0), stride, C.c_void_p(len_ptr or 0)), "zkp_fr_merkle_paths_dev")
 
+    def sha256_dev(self, msgs_ptr: int, n: int, length: int, out_ptr: int):
+        """zkp_sha256_dev: the digests of n row-major DEVICE messages of `length` bytes, 32 bytes each.  One launch."""
+        _lib.check(self.lib.zkp_sha256_dev(self.h, C.c_void_p(msgs_ptr or 0), n, length, C.c_void_p(out_ptr or 0)), "zkp_sha256_dev")
+
+    def sha256_trace_dev(self, msgs_ptr: int, n: int, length: int, trace_ptr: int):
+        """zkp_sha256_trace_dev: the canonical trace of the same messages, sha256.trace_words(length) * n uint32.  One launch."""
+        _lib.check(self.lib.zkp_sha256_trace_dev(self.h, C.c_void_p(msgs_ptr or 0), n, length, C.c_void_p(trace_ptr or 0)),
+                   "zkp_sha256_trace_dev")
+
+    def sha256_merkle_tree_dev(self, nodes_ptr: int, n: int):
+        """zkp_sha256_merkle_tree_dev: fills the inner nodes [0, n - 1) of 2 n - 1 items of 32 bytes, the leaves at [n - 1, 2 n - 1)."""
+        _lib.check(self.lib.zkp_sha256_merkle_tree_dev(self.h, C.c_void_p(nodes_ptr or 0), n), "zkp_sha256_merkle_tree_dev")
+
+    def fr_bits_expand_dev(self, curve, trace_ptr: int, words_per_msg: int, msgs_per_instance: int, q: int, code_ptr: int, m: int,
+                           max_v: int, z_ptr: int, z_stride: int):
+        """zkp_fr_bits_expand_dev: z[b * z_stride + j] = the bit that code[j] selects from instance b's messages, as Montgomery 0 / 1."""
+        _lib.check(self.lib.zkp_fr_bits_expand_dev(self.h, get_curve(curve).cid, C.c_void_p(trace_ptr or 0), words_per_msg,
+                                                   msgs_per_instance, q, C.c_void_p(code_ptr or 0), m, max_v, C.c_void_p(z_ptr or 0),
+                                                   z_stride), "zkp_fr_bits_expand_dev")
+
     def fr_prefix_product_dev(self, curve, in_ptr: int, out_ptr: int, n: int, want_total: bool = True):
         """zkp_fr_prefix_product_dev: out[0] = 1, out[i] = in[0] ... in[i-1] over n DEVICE Montgomery Fr (out may be in).
         Returns the (4,) uint64 Montgomery product of all n, or None without want_total."""

@@ -50,7 +50,8 @@ UNITS = [("ntt.hip", "ntt.o", ["-DZKP_INLINE_MUL"]),
          ("hyrax.hip", "hyrax.o", ["-DZKP_INLINE_MUL"]),           # Hyrax data-parallel GKR: sum-check over the copies + batched layer evaluation, Fr only likewise
          ("bulletproofs.hip", "bulletproofs.o", ["-DZKP_INLINE_MUL"]),   # Bulletproofs R1CS prover: powers, fused l(X) / r(X) + IPA a / b fold, Fr only likewise
          ("asvc.hip", "asvc.o", ["-DZKP_INLINE_MUL"]),             # aSVC: subset weights + the quotient by a subvector's vanishing polynomial, Fr only likewise
-         ("fr_hash.hip", "fr_hash.o", ["-DZKP_INLINE_MUL"])]       # MiMC / Poseidon / Rescue permutations, one lane per block, + CBMT Merkle trees, Fr only likewise
+         ("fr_hash.hip", "fr_hash.o", ["-DZKP_INLINE_MUL"]),       # MiMC / Poseidon / Rescue permutations, one lane per block, + CBMT Merkle trees, Fr only likewise
+         ("sha256.hip", "sha256.o", [])]                           # SHA-256 digests, traces + CBMT trees and the bit-witness expansion: no field arithmetic, both curves in one object
 for _c, _g in CONFIGS:
     _d = [f"-DZKP_CFG_CURVE={_c}", f"-DZKP_CFG_GROUP={_g}"]
     UNITS.append(("msm_group.hip", f"msm_group_c{_c}{_g}.o", _d + (["-DZKP_INLINE_MUL"] if (_c, _g) in ((0, 1), (0, 2), (1, 1)) else [])))

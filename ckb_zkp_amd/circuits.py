@@ -5,6 +5,11 @@
                 10 constraints per sample; the image is `alloc`ed, so the only input is the constant one).
 * `mimc_chain_instance` — the same system written directly as arrays (no per-constraint closures) for the
   2^20 .. 2^24 benchmark instances of BASELINE.json (S = floor((2^k - 1)/10) samples -> domain 2^k).
+* `Sha256Block`  — gadgets/src/hashes/sha256.rs:404-428 (`test_full_block`: 512 allocated bits, one compression from the IV).
+* `Sha256Merkle` — gadgets/examples/merkle_tree_sha256.rs:32-73 (membership of a 32-byte leaf under SHA-256 merges; the root's 256
+                   bits are the public inputs).
+  Both name the messages whose canonical traces hold every value of their assignment (`messages`, `message_len`), for
+  sha256.synthesize / sha256.witness_dev.
 """
 from __future__ import annotations
 
@@ -53,6 +58,53 @@ class MimcChain:
                 cs.enforce(lambda lc: lc + tmp, lambda lc: lc + xl + (ci, cs.one()), lambda lc: lc + new_xl - xr)
                 xr, xr_v = xl, xl_v
                 xl, xl_v = new_xl, new_v
+
+
+class Sha256Block:
+    """bits512: 512 booleans, most significant bit of byte 0 first (None: no values).  Its one message is the 64 bytes the bits
+    spell; the circuit is the first of that message's two blocks."""
+    messages, message_len = 1, 64
+
+    def __init__(self, bits512=None):
+        self.bits = [None] * 512 if bits512 is None else [bool(b) for b in bits512]
+        assert len(self.bits) == 512
+
+    def message_bytes(self) -> list:
+        return [bytes(sum(int(self.bits[8 * k + i]) << (7 - i) for i in range(8)) for k in range(64))]
+
+    def generate_constraints(self, cs):
+        from .bits import AllocatedBit, Boolean
+        from .sha256 import input_bit_tags, sha256_block_no_padding
+        tags = input_bit_tags(0, 0, 64)
+        bits = [Boolean.is_(AllocatedBit.alloc(cs, v, tags[p])) for p, v in enumerate(self.bits)]
+        self.output = sha256_block_no_padding(cs, bits, 0)
+
+
+class Sha256Merkle:
+    """index: the heap index of the leaf (n - 1 + its position among n leaves, MerkleProof.index); leaf, root: 32 bytes; lemmas:
+    the siblings from the leaf upwards, 32 bytes each.  None for leaf / root / a lemma: no value (key generation).  The shape of
+    the circuit depends on index: which half of each message is the path's node.  Its messages are merkle.membership_messages."""
+    message_len = 64
+
+    def __init__(self, index: int, leaf, lemmas, root):
+        self.index, self.leaf, self.lemmas, self.root = index, leaf, list(lemmas), root
+        self.messages = len(self.lemmas)
+
+    def generate_constraints(self, cs):
+        from .merkle import MerkleProofGadget
+        from .sha256 import AbstractHashSha256Output as Out, digest_bit_tags, input_bit_tags, trace_words
+        W, d = trace_words(self.message_len), self.messages
+
+        def data(b):
+            return 32 if b is None else bytes(b)
+
+        var_root = Out.alloc_input(cs, data(self.root), digest_bit_tags((d - 1) * W, self.message_len) if d else None)
+        var_leaf = Out.alloc(cs, data(self.leaf), input_bit_tags(0, 0 if self.index & 1 else 32, 32) if d else None)
+        lemmas, index = [], self.index
+        for j, v in enumerate(self.lemmas):
+            lemmas.append(Out.alloc(cs, data(v), input_bit_tags(j * W, 32 if index & 1 else 0, 32)))
+            index = (index - 1) >> 1
+        MerkleProofGadget(self.index, lemmas).set_membership(cs, var_root, var_leaf, W)
 
 
 def splitmix64(state: int):

@@ -18,6 +18,7 @@
 #include "g1_ntt.hpp"
 #include "pedersen.hpp"
 #include "plonk.hpp"
+#include "sha256.hpp"
 #include "spark.hpp"
 #include "stream_place.hpp"
 #include "sumcheck.hpp"
@@ -998,6 +999,28 @@ int32_t zkp_fr_merkle_paths_dev(zkp_ctx* ctx, const uint64_t* nodes_dev, size_t 
                                 uint64_t* out_dev, size_t stride, uint32_t* len_dev) {
   if (!nodes_dev || !leaf_idx_dev || !out_dev || !len_dev) return ZKP_ERR_BAD_ARG;
   return guarded(ctx, [&] { fr_merkle_paths(ctx, nodes_dev, n, leaf_idx_dev, q, out_dev, stride, len_dev); });
+}
+int32_t zkp_sha256_info(uint64_t* info) {
+  if (!info) return ZKP_ERR_BAD_ARG;
+  sha256_info(info);
+  return ZKP_OK;
+}
+int32_t zkp_sha256_dev(zkp_ctx* ctx, const uint8_t* msgs_dev, size_t n, size_t len, uint8_t* out_dev) {
+  if (!msgs_dev || !out_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { sha256_digests(ctx, msgs_dev, n, len, out_dev); });
+}
+int32_t zkp_sha256_trace_dev(zkp_ctx* ctx, const uint8_t* msgs_dev, size_t n, size_t len, uint32_t* trace_dev) {
+  if (!msgs_dev || !trace_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { sha256_trace(ctx, msgs_dev, n, len, trace_dev); });
+}
+int32_t zkp_sha256_merkle_tree_dev(zkp_ctx* ctx, uint8_t* nodes_dev, size_t n) {
+  if (!nodes_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { sha256_merkle_tree(ctx, nodes_dev, n); });
+}
+int32_t zkp_fr_bits_expand_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint32_t* trace_dev, size_t words_per_msg, size_t msgs_per_instance,
+                               size_t q, const uint32_t* code_dev, size_t m, uint32_t max_v, uint64_t* z_dev, size_t z_stride) {
+  if (!trace_dev || !code_dev || !z_dev) return ZKP_ERR_BAD_ARG;
+  return guarded(ctx, [&] { fr_bits_expand(ctx, curve, trace_dev, words_per_msg, msgs_per_instance, q, code_dev, m, max_v, z_dev, z_stride); });
 }
 int32_t zkp_bench_mulmod(zkp_ctx* ctx, zkp_curve_t curve, int32_t field, int32_t unsaturated, double* out) {
   if (!out || (curve != ZKP_BN254 && curve != ZKP_BLS12_381) || field < 0 || field > 1) return ZKP_ERR_BAD_ARG;

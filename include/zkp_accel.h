@@ -63,7 +63,9 @@ const char* zkp_status_string(int32_t status);
  * then zkp_hash_params_create / zkp_hash_params_free / zkp_hash_params_info / zkp_fr_hash_blocks_dev / zkp_fr_hash_chain_dev /
  * zkp_fr_mimc_trace_dev / zkp_fr_merkle_tree_dev / zkp_fr_merkle_paths_dev (MiMC, Poseidon and Rescue hashing, CBMT Merkle trees),
  * then zkp_pairing_info / zkp_pairing_miller_dev / zkp_pairing_final_exp_dev / zkp_pairing_product_is_one_dev / zkp_pairing /
- * zkp_pairing_check (optimal-ate pairings: the Groth16 and KZG10 verifiers).
+ * zkp_pairing_check (optimal-ate pairings: the Groth16 and KZG10 verifiers),
+ * then zkp_sha256_info / zkp_sha256_dev / zkp_sha256_trace_dev / zkp_sha256_merkle_tree_dev / zkp_fr_bits_expand_dev (SHA-256
+ * digests, traces and Merkle trees, and the witness of a bit circuit).
  * 0.7: zkp_msm_g1_var_batch_dev / zkp_msm_g2_var_batch_dev (batched small variable-base MSMs).
  * 0.6 (round 6): zkp_ctx_config / zkp_ctx_create_ex / zkp_ctx_create_multi_ex / zkp_ctx_get_config (the
  * prover switches are per context; the environment only supplies defaults, read when the context is created); RCCL bring-up behind a
@@ -648,6 +650,61 @@ int32_t zkp_fr_merkle_tree_dev(zkp_ctx* ctx, const zkp_hash_params* params, int3
 #define ZKP_MERKLE_BAD_LEAF 4294967295u
 int32_t zkp_fr_merkle_paths_dev(zkp_ctx* ctx, const uint64_t* nodes_dev, size_t n, const uint32_t* leaf_idx_dev, size_t q,
                                 uint64_t* out_dev, size_t stride, uint32_t* len_dev);
+/* SHA-256 and the witness of bit circuits (later in 0.7.1, detected by symbol): the byte hash behind the reference's sha256 gadget
+ * (gadgets/src/hashes/sha256.rs) and its Merkle-membership example (gadgets/examples/merkle_tree_sha256.rs), and the producer of
+ * that circuit's device-resident witness for zkp_groth16_prove_dev.  No field arithmetic: the curve enters the last entry only.
+ * Pointers are DEVICE memory, 16-byte aligned.  Every argument is checked before anything runs: on an error the outputs are
+ * untouched.  All of them run on the context's current stream and only launch: no host work proportional to n.
+ *
+ * The canonical trace of n messages of len bytes is uint32 T[w n + k], word w < W, message k < n, with
+ * W = 1 + ZKP_SHA256_BLOCK_WORDS ceil((len + 9) / 64).  Word 0 is 0.  Block b of the padded message owns the ZKP_SHA256_BLOCK_WORDS
+ * words from 1 + ZKP_SHA256_BLOCK_WORDS b, at the offsets that zkp_sha256_info reports:
+ *   input + j, j < 16             the block's input words, as SHA-256 reads them
+ *   sched + 6 (i - 16), i = 16..63  rotr7 ^ rotr18 of w[i-15]; that ^ shr3; rotr17 ^ rotr19 of w[i-2]; that ^ shr10; the integer
+ *                                 w[i-16] + s0 + w[i-7] + s1 as lo, hi
+ *   round + 11 i, i < 64          the integer that forms the round's e as lo, hi; rotr6 ^ rotr11 of e; that ^ rotr25; ch; the integer
+ *                                 that forms the round's a as lo, hi; rotr2 ^ rotr13 of a; that ^ rotr22; maj; b & c.  In round 0 the
+ *                                 two integers are the incoming state words, hi = 0
+ *   final + 2 k, k < 8            the integer h_k as lo, hi; h0 and h4 fold the operands that round 63 deferred (8 and 7 operands)
+ * The integers are the full sums, not reduced mod 2^32: the gadget allocates their carry bits (uint32.rs:285-357).
+ *
+ * zkp_sha256_info: info[16] = words per block, input offset, sched offset, words per sched record, round offset, words per round
+ * record, final offset, ZKP_SHA256_MAX_LOG_LEN, _BYTES, _TRACE_WORDS, _LEAVES, _CODE_WORDS, the lanes of a hashing workgroup, the
+ * lanes of an expanding workgroup, 0, 0. */
+#define ZKP_SHA256_BLOCK_WORDS 1024
+#define ZKP_SHA256_MAX_LOG_LEN 20
+#define ZKP_SHA256_MAX_LOG_BYTES 34
+#define ZKP_SHA256_MAX_LOG_TRACE_WORDS 32
+#define ZKP_SHA256_MAX_LOG_LEAVES 27
+#define ZKP_SHA256_MAX_LOG_CODE_WORDS 26
+int32_t zkp_sha256_info(uint64_t* info);
+/* out[32 k, 32 k + 32) = SHA-256 of the len bytes at msgs + k len, in digest byte order.  0 <= len <= 2^ZKP_SHA256_MAX_LOG_LEN,
+ * n >= 1, n (len + 1) <= 2^ZKP_SHA256_MAX_LOG_BYTES.  The messages are not written; out overlaps them nowhere.  One launch, one
+ * lane per message. */
+int32_t zkp_sha256_dev(zkp_ctx* ctx, const uint8_t* msgs_dev, size_t n, size_t len, uint8_t* out_dev);
+/* The canonical trace of the same n messages: W n words to trace_dev.  The rules of zkp_sha256_dev, and
+ * W n <= 2^ZKP_SHA256_MAX_LOG_TRACE_WORDS.  One launch. */
+int32_t zkp_sha256_trace_dev(zkp_ctx* ctx, const uint8_t* msgs_dev, size_t n, size_t len, uint32_t* trace_dev);
+/* The complete binary Merkle tree of cbmt.rs:182-202 over 32-byte items with merge(l, r) = SHA-256(l || r): nodes_dev holds 2 n - 1
+ * items with the n leaves already at [n - 1, 2 n - 1); the call fills [0, n - 1); nodes[0] is the root.  Any 1 <= n <=
+ * 2^ZKP_SHA256_MAX_LOG_LEAVES; n == 1 launches nothing.  One launch per depth of inner nodes, one lane per node, two compressions
+ * per lane.  Membership paths need no entry of their own: zkp_fr_merkle_paths_dev is a gather of 32-byte nodes without arithmetic
+ * and serves such a tree as it stands. */
+int32_t zkp_sha256_merkle_tree_dev(zkp_ctx* ctx, uint8_t* nodes_dev, size_t n);
+/* The witness of a bit circuit from a trace: z[b z_stride + j] = bit ^ neg for b < q, j < m, as zero or the Montgomery one of
+ * `curve`, where code_dev[j] = v << 6 | bit << 1 | neg (uint32) selects bit `bit` of word v % words_per_msg of message
+ * v / words_per_msg of instance b, and trace_dev is the trace of q msgs_per_instance messages, those of instance b at
+ * [b msgs_per_instance, (b + 1) msgs_per_instance).  Code 0 is the constant 0 and code 1 the constant 1 (word 0 of a trace is 0).
+ * max_v: the largest v among the codes, which the CALLER states (a driver computes it once, when it uploads the codes);
+ * max_v >= words_per_msg msgs_per_instance -> ZKP_ERR_BAD_ARG.  The codes themselves are not read on the host; a code whose v lies
+ * outside the instance's words although max_v said otherwise reads nothing and gives its bare neg.  words_per_msg msgs_per_instance <= 2^ZKP_SHA256_MAX_LOG_CODE_WORDS, that times q <= 2^ZKP_SHA256_MAX_LOG_TRACE_WORDS,
+ * q >= 1, m >= 1, z_stride >= m, q z_stride <= 2^32; the elements of a gap between two instances are not written.  z overlaps
+ * neither input.  One launch, 32 bytes per lane in two 16-byte stores.  The entry knows nothing of SHA-256: any bit circuit whose
+ * values are bits of a word-major trace can use it.
+ * ZKP_ERR_BAD_ARG of the four entries above: a NULL or misaligned pointer, a count of 0 or above its cap, a stride too small,
+ * spans that overlap against the rules; ZKP_ERR_UNSUPPORTED_CURVE: another curve. */
+int32_t zkp_fr_bits_expand_dev(zkp_ctx* ctx, zkp_curve_t curve, const uint32_t* trace_dev, size_t words_per_msg, size_t msgs_per_instance,
+                               size_t q, const uint32_t* code_dev, size_t m, uint32_t max_v, uint64_t* z_dev, size_t z_stride);
 /* Optimal-ate pairings (later in 0.7.1, detected by symbol): products of Miller functions and the final exponentiation on BN254 and
  * BLS12-381, the primitive of groth16::verify_proof (groth16/src/verifier.rs:8-44), KZG10::check (marlin/src/pc/kzg10.rs:158-173)
  * and the aSVC checks.  n pairs (P_i, Q_i) form m = n / group groups of `group` consecutive pairs; a group's value is the product of
